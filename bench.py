@@ -1,15 +1,21 @@
 #!/usr/bin/env python
 """bench.py -- ref-scenes/s of the MI355X plane-sweep hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]                    (N > 1 without WORLD_SIZE: bench.py starts its own N ranks)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1 without WORLD_SIZE: bench.py starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one CascadeMVSNet_eval.forward at batch 1 = one reference view ("ref-scene") of
 BASELINE config 2: DTU-shaped, 3 views, 512x640, D = 48/32/8, fp32, synthetic seeded inputs and
 weights already resident in HBM.  Reference views are independent, so N GPUs run N independent
-streams of scenes with no data-path collective ("weak" scaling): value = N*K / max-over-ranks time.
+streams of scenes with no data-path collective ("weak" scaling): value = N*K / max-over-ranks time
+of exactly K timed steps between barrier + synchronize pairs, after W untimed warm-up steps.
 
-The JSON line also carries
+A plain run does only that: set up, warm up, time the K steps, write the last step's outputs when
+--dump-outputs DIR is given (DIR/<name>.npy, float32 / float64, <= 64 MB in all: a fixed seeded
+sample of larger outputs), print one JSON line.  Seeded inputs make the outputs of two builds
+comparable array for array.
+
+With --full the JSON line also carries
   roofline      the fused warp+variance kernel (K1): algorithmic bytes of its three per-scene
                 launches (137.6 + 194.0 + 125.8 MB) / their HIP-event durations
                 recorded on the launch stream in a separate pass over the same scenes right after the timed region
@@ -24,8 +30,7 @@ The JSON line also carries
   train_step    a short timing of the config-3 training iteration (5 iterations after 2 warm-ups; --no-train-step skips it);
   two_procs_per_gpu      N = 1 only, a side pass after the timed region, never `value`: `bench.py --procs-per-gpu 2` run as a child -- two worker
                 processes on the GPU, whole scenes each (--no-side-pass skips it);
-  timed_rounds  when K steps take less than 0.5 s the barrier-bracketed region of exactly K steps is repeated and the MEDIAN round is
-                reported (`value`, `ms_per_step`, `timed_region_s`), so that a short --steps still keeps the GPU busy for half a second;
+  per_rank_scenes_per_s  N > 1: every rank's own rate over the timed steps (min / max);
   cpu_baseline  the oracle's ATen op graph (= the reference's CPU path) timed on the host cores
                 of this box on a bounded sample, rank 0, N=1 only -- a reported baseline, plus
                 the depth-L1 parity of the HIP output against it on the same inputs.
@@ -36,8 +41,8 @@ reference's losses, one backward, Adam) -- with N > 1 ranks as data-parallel tra
 models, gradients of both models averaged with ONE reduce-scatter + all-gather message over RCCL (parallel.GradSync).
 ``--workload unsup_loss`` / ``--workload fusion`` time the two callers either side of the path that SURVEY.md section 8f ranks
 next (the self-supervised loss of the training step, the depth-map fusion filter of the evaluation) with the same contract and
-their own ``roofline`` / ``cpu_baseline`` objects; the default workload, and the only one BASELINE.json's metric is quoted
-on, is the cascade.
+their own ``roofline`` / ``cpu_baseline`` objects (with --full); the default workload, and the only one BASELINE.json's metric is
+quoted on, is the cascade.
 """
 import argparse
 import json
@@ -182,61 +187,75 @@ def k1_algorithmic_bytes():
     return per_stage
 
 
-MIN_TIMED_S = 0.5               # a timed region shorter than this is repeated in rounds (each exactly K steps) and the median round reported
-MIN_TIMED_S_SHORT = 6.0         # ... and with --steps < 100 (the driver's --steps 20 is ~23 ms of cascade forwards) rounds are repeated for 6 s, so that a
-                                # utilisation sampler with a 5-second period sees a busy GPU (BENCH_r05.gpu_busy had 0 of 5 samples active)
-MAX_ROUNDS = 4000
-
-
-def timed_rounds(world, dev, steps, step, sync):
-    """The contract's timed region -- exactly K steps between barrier + synchronize pairs, max over ranks -- repeated while the
-    rounds so far add up to less than MIN_TIMED_S (the driver's --steps 20 is 28 ms of cascade forwards: too short for an external
-    utilisation sampler to see the GPU busy).  Returns (median round's max-over-ranks seconds, this rank's own seconds of that
-    round, every round's max-over-ranks seconds).  The process group stays up."""
+def timed_steps(world, dev, steps, step, sync):
+    """The contract's timed region: exactly K steps between barrier + synchronize pairs, max over ranks.  Returns (max-over-ranks
+    seconds, this rank's own seconds).  The process group stays up."""
     import torch.distributed as dist
-    rounds, owns = [], []
-    while True:
-        sync()
-        if world > 1:
-            dist.barrier()
-        sync()
-        t0 = time.perf_counter()
-        for i in range(steps):
-            step(i)
-        sync()
-        own = time.perf_counter() - t0
-        if world > 1:
-            dist.barrier()
-        elapsed = time.perf_counter() - t0
-        if world > 1:
-            t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)          # every rank sees the same round time, hence takes the same decision below
-            elapsed = float(t.item())
-        rounds.append(elapsed)
-        owns.append(own)
-        if sum(rounds) >= (MIN_TIMED_S_SHORT if (steps < 100 and dev.type == "cuda") else MIN_TIMED_S) or len(rounds) >= MAX_ROUNDS:
-            break
-    order = sorted(range(len(rounds)), key=lambda i: rounds[i])
-    mid = order[len(order) // 2]
-    return rounds[mid], owns[mid], rounds
-
-
-def rounds_fields(rounds):
-    return {"timed_rounds": len(rounds), "rounds_total_s": round(sum(rounds), 4),
-            "round_s_min_max": [round(min(rounds), 5), round(max(rounds), 5)]}
+    sync()
+    if world > 1:
+        dist.barrier()
+    sync()
+    t0 = time.perf_counter()
+    for i in range(steps):
+        step(i)
+    sync()
+    own = time.perf_counter() - t0
+    if world > 1:
+        dist.barrier()
+    elapsed = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    return elapsed, own
 
 
 def timed_region(world, dev, warmup, steps, step):
-    """W untimed steps, then timed_rounds; tears the process group down.  Returns (median round seconds, all rounds)."""
+    """W untimed steps, then timed_steps; tears the process group down.  Returns the max-over-ranks seconds of the K steps."""
     import torch.distributed as dist
     for i in range(warmup):
         step(i)
     sync = torch.cuda.synchronize if dev.type == "cuda" else (lambda: None)
-    elapsed, _, rounds = timed_rounds(world, dev, steps, step, sync)
+    elapsed, _ = timed_steps(world, dev, steps, step, sync)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    return elapsed, rounds
+    return elapsed
+
+
+DUMP_MAX_BYTES = 64 * 10**6           # all .npy files of a dump together, headers included
+NPY_HEADER_BYTES = 1024                # an upper bound of one .npy file's header
+
+
+def _output_leaves(name, x):
+    """(dotted name, value) of every tensor / number in a nest of dicts, lists and tuples."""
+    if isinstance(x, dict):
+        for k, v in x.items():
+            yield from _output_leaves(f"{name}.{k}" if name else str(k), v)
+    elif isinstance(x, (list, tuple)):
+        for i, v in enumerate(x):
+            yield from _output_leaves(f"{name}.{i}" if name else str(i), v)
+    elif torch.is_tensor(x) or isinstance(x, (int, float)):
+        yield name or "output", x
+
+
+def dump_outputs(out_dir, outputs):
+    """Write what a caller of the timed path received from its last step as out_dir/<name>.npy: float64 / 64-bit integers as
+    float64, everything else as float32.  When the files would exceed DUMP_MAX_BYTES in all, every array is cut to the same share of its
+    elements, picked by a fixed seed (flattened, in index order), so that two runs with the same arguments write the same sample."""
+    import numpy as np
+    arrays = {}
+    for name, v in _output_leaves("", outputs):
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        arrays[name] = a.astype(np.float64 if a.dtype in (np.float64, np.int64, np.uint64) else np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_MAX_BYTES - NPY_HEADER_BYTES * len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > budget:
+            n = max(1, a.size * budget // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def two_procs_side_pass(steps):
@@ -245,14 +264,14 @@ def two_procs_side_pass(steps):
     from rc_mvsnet_amd.sharding import clean_env
     env = clean_env()
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--procs-per-gpu", "2", "--steps", str(steps), "--warmup", "10",
-           "--no-cpu-baseline", "--no-train-step", "--no-side-pass"]
+           "--full", "--no-cpu-baseline", "--no-train-step", "--no-side-pass"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     if out.returncode != 0 or not lines:
         return {"error": f"child exited with {out.returncode}: {out.stderr[-300:]}"}
     b = json.loads(lines[-1])
     return {"value": b["value"], "unit": b["unit"], "ms_per_step": b["ms_per_step"], "steps_per_process": b["steps"], "processes": 2,
-            "per_rank_scenes_per_s": b.get("per_rank_scenes_per_s"), "timed_rounds": b.get("timed_rounds"),
+            "per_rank_scenes_per_s": b.get("per_rank_scenes_per_s"),
             "note": "side pass, NOT `value`: two worker processes on the one GPU, each running whole scenes one at a time (python bench.py --procs-per-gpu 2)"}
 
 
@@ -288,13 +307,22 @@ def bench_unsup_loss(args, rank, world, dev):
 
     def step(i):
         inputs = {k: {"depth": v.clone().requires_grad_(True)} for k, v in gd.items()}
-        total, _ = mod(inputs, gi, gc, dlossw=[0.5, 1.0, 2.0])
+        total, scalars = mod(inputs, gi, gc, dlossw=[0.5, 1.0, 2.0])
         total.backward()
-        last["total"] = total
+        last.update(total=total, scalars=scalars, depth_grad={k: v["depth"].grad for k, v in inputs.items()})
 
-    elapsed, rounds = timed_region(world, dev, args.warmup, args.steps, step)
+    elapsed = timed_region(world, dev, args.warmup, args.steps, step)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    result = {"metric": "loss steps/sec (UnsupLossMultiStage forward+backward, 4 views 512x640, 3 stages)", "value": round(world * args.steps / elapsed, 2),
+              "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+              "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+              "config": {"workload": "SURVEY 8f-2: losses/unsup_loss.py UnsupLossMultiStage on BASELINE configs[2] shapes (batch 1 per GPU)",
+                         "views": Vl, "height": H, "width": W, "parallelism": f"sample-per-gpu x{world}"}}
+    if not args.full:
+        return result
     # dominant launch group: one full-resolution stage forward (rcmvs_unsup_loss_fwd, 2 Vs + 3 launches)
     Vs = Vl - 1
     ref = losses.stage_image(gi[:, 0], 2)
@@ -306,12 +334,7 @@ def bench_unsup_loss(args, rank, world, dev):
                 "achieved": round(alg / (ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(alg / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": None, "algorithmic_bytes": alg,
                 "us": round(ms * 1e3, 1), "note": "9 short launches over 0.33 M pixels: launch / latency bound, not bandwidth bound"}
-    result = {"metric": "loss steps/sec (UnsupLossMultiStage forward+backward, 4 views 512x640, 3 stages)", "value": round(world * args.steps / elapsed, 2),
-              "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-              "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-              "config": {"workload": "SURVEY 8f-2: losses/unsup_loss.py UnsupLossMultiStage on BASELINE configs[2] shapes (batch 1 per GPU)",
-                         "views": Vl, "height": H, "width": W, "parallelism": f"sample-per-gpu x{world}"},
-              "roofline": roofline, **rounds_fields(rounds)}
+    result["roofline"] = roofline
     if world == 1 and not args.no_cpu_baseline:
         from oracle import unsup_loss as O
         nthreads = host_threads()
@@ -351,24 +374,28 @@ def bench_fusion(args, rank, world, dev):
 
     def step(i):
         r = fuse(i)
-        xyz, _ = fusion.compact_points(r["masks"][2], r["xyz"], r["rgb"])
-        kept["n"] = len(xyz)
+        xyz, rgb = fusion.compact_points(r["masks"][2], r["xyz"], r["rgb"])
+        kept.update(n=len(xyz), out={**r, "points_xyz": xyz, "points_rgb": rgb})
 
-    elapsed, rounds = timed_region(world, dev, args.warmup, args.steps, step)
+    elapsed = timed_region(world, dev, args.warmup, args.steps, step)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, kept["out"])
+    result = {"metric": "fused reference views/sec (filter_depth body, 1184x1600, 10 source views)", "value": round(world * args.steps / elapsed, 1),
+              "unit": "ref-views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+              "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+              "config": {"workload": "SURVEY 8f-3: eval_rcmvsnet_dtu.py filter_depth per-reference-view body, DTU evaluation shape", "height": Hf,
+                         "width": Wf, "source_views": n_src, "points_kept": kept.get("n"), "parallelism": f"scan-per-gpu x{world}"}}
+    if not args.full:
+        return result
     ms = event_ms(lambda: fuse(0))
     alg = Hf * Wf * (4 + 4 + 12 + 4 * n_src + 3 + 4 + 12 + 3)        # depth, conf, img, each source map once; masks, avg, xyz, rgb
     roofline = {"bound": "hbm", "kernel": "rcmvs::fuse_view_kernel (1 launch per reference view)", "achieved": round(alg / (ms * 1e-3) / 1e9, 1),
                 "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(alg / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": None,
                 "algorithmic_bytes": alg, "us": round(ms * 1e3, 1),
                 "note": "fp64 chain with fp32 cast points, ~250 fp64 operations per (pixel, source view): closer to the fp64 vector rate than to HBM"}
-    result = {"metric": "fused reference views/sec (filter_depth body, 1184x1600, 10 source views)", "value": round(world * args.steps / elapsed, 1),
-              "unit": "ref-views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-              "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-              "config": {"workload": "SURVEY 8f-3: eval_rcmvsnet_dtu.py filter_depth per-reference-view body, DTU evaluation shape", "height": Hf,
-                         "width": Wf, "source_views": n_src, "points_kept": kept.get("n"), "parallelism": f"scan-per-gpu x{world}"},
-              "roofline": roofline, **rounds_fields(rounds)}
+    result["roofline"] = roofline
     if world == 1 and not args.no_cpu_baseline:
         from oracle import fusion as O
         ref, srcs = s["pairs"][0]
@@ -402,9 +429,23 @@ def bench_train_step(args, rank, world, dev):
     def step(i):
         last.update(ts.train_step(model, model_nerf, opt, imgs, proj, dv, batch, grad_sync=sync))
 
-    elapsed, rounds = timed_region(world, dev, args.warmup, args.steps, step)
+    elapsed = timed_region(world, dev, args.warmup, args.steps, step)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"losses": last, "model": dict(model.named_parameters()), "model_nerf": dict(model_nerf.named_parameters())})
+    result = {"metric": "training iterations/sec (DTU-shaped 4 views 512x640, D=48/32/8, rendering branch 1024 rays x 128 samples)",
+              "value": round(world * args.steps / elapsed, 3), "unit": "iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+              "ms_per_step": round(elapsed / args.steps * 1e3, 3), "timed_region_s": round(elapsed, 4), "higher_is_better": True, "scaling": "weak",
+              "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+              "config": {"workload": f"BASELINE configs[{2 if world == 1 else 3}]: train_rcmvsnet.py iteration (2 x CascadeMVSNet.forward, "
+                                     "Rendering_Consistency_Net.forward, UnsupLoss + AugLoss + render losses, backward, Adam), batch 1 per GPU",
+                         "views": Vt, "height": H, "width": W, "ndepths": list(NDEPTHS), "rays": 1024, "samples": 128,
+                         "parallelism": f"dp{world}" + (" (SyncBatchNorm + one reduce-scatter/all-gather gradient message over RCCL)" if world > 1 else ""),
+                         "rccl_ranks": world, "gpus": args.gpus},
+              "losses": {k: round(v, 5) for k, v in last.items()}}
+    if not args.full:
+        return result
     # dominant memory-bound kernel of the iteration: the K1 backward scatter at stage 3 (two calls per iteration)
     C, D, h, w = FEAT_C[2], NDEPTHS[2], H, W
     g = torch.Generator().manual_seed(0)
@@ -419,16 +460,7 @@ def bench_train_step(args, rank, world, dev):
                 "achieved": round(alg / (ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(alg / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": None, "algorithmic_bytes": alg, "us": round(ms * 1e3, 1),
                 "note": "4 fp32 atomics per (tap, channel quad): atomic-rate bound, not bandwidth bound"}
-    result = {"metric": "training iterations/sec (DTU-shaped 4 views 512x640, D=48/32/8, rendering branch 1024 rays x 128 samples)",
-              "value": round(world * args.steps / elapsed, 3), "unit": "iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-              "ms_per_step": round(elapsed / args.steps * 1e3, 3), "timed_region_s": round(elapsed, 4), "higher_is_better": True, "scaling": "weak",
-              "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-              "config": {"workload": f"BASELINE configs[{2 if world == 1 else 3}]: train_rcmvsnet.py iteration (2 x CascadeMVSNet.forward, "
-                                     "Rendering_Consistency_Net.forward, UnsupLoss + AugLoss + render losses, backward, Adam), batch 1 per GPU",
-                         "views": Vt, "height": H, "width": W, "ndepths": list(NDEPTHS), "rays": 1024, "samples": 128,
-                         "parallelism": f"dp{world}" + (" (SyncBatchNorm + one reduce-scatter/all-gather gradient message over RCCL)" if world > 1 else ""),
-                         "rccl_ranks": world, "gpus": args.gpus},
-              "roofline": roofline, "losses": {k: round(v, 5) for k, v in last.items()}, **rounds_fields(rounds)}
+    result["roofline"] = roofline
     if world == 1 and not args.no_cpu_baseline:
         # bounded sample of the reference's CPU path: forward + backward of ONE of the iteration's two CascadeMVSNet passes
         # (oracle/aten_graph.py on the host cores); the iteration has two of them plus the renderer and the losses, so
@@ -452,7 +484,7 @@ def bench_train_step(args, rank, world, dev):
 
 def bench_stub(args, rank, world, dev):
     """The contract without a GPU (tests/test_bench_contract_cpu.py): a step is one small CPU matmul, ranks rendezvous over gloo.  Exercises
-    what the real workloads share -- the self-spawn of N ranks, the barrier-bracketed rounds, max over ranks, one JSON line from rank 0."""
+    what the real workloads share -- the self-spawn of N ranks, the barrier-bracketed timed steps, max over ranks, one JSON line from rank 0."""
     x = torch.randn(64, 64, generator=torch.Generator().manual_seed(rank))
     acc = {"n": 0}
 
@@ -460,14 +492,16 @@ def bench_stub(args, rank, world, dev):
         acc["y"] = x @ x
         acc["n"] += 1
 
-    elapsed, rounds = timed_region(world, dev, args.warmup, args.steps, step)
+    elapsed = timed_region(world, dev, args.warmup, args.steps, step)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": acc["y"]})
     return {"metric": "stub steps/sec (64x64 CPU matmul; contract self-test, not a benchmark)", "value": round(world * args.steps / elapsed, 3),
             "unit": "steps/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 6),
             "timed_region_s": round(elapsed, 6), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "stub", "parallelism": f"x{world}", "ranks": world, "procs_per_gpu": args.procs_per_gpu},
-            "steps_run_by_rank0": acc["n"], **rounds_fields(rounds)}
+            "steps_run_by_rank0": acc["n"]}
 
 
 def main(argv=None):
@@ -482,13 +516,19 @@ def main(argv=None):
                          "GPU overlap each other's latency-bound phases like HIP streams would, without sharing an address space")
     ap.add_argument("--shape", default="dtu_bench", choices=sorted(SHAPES),
                     help="cascade workload: dtu_bench = BASELINE configs[1] (the metric's configuration, default); dtu_eval = the reference's DTU evaluation shape "
-                         "(5 views, 1184x1600); tanks = configs[4]'s single-GPU workload (7 views, 1056x1920, D=64/32/8).  The other shapes print a full line "
-                         "(roofline with that shape's algorithmic bytes, parity against the oracle on a down-scaled twin) without the CPU timing / side passes.")
+                         "(5 views, 1184x1600); tanks = configs[4]'s single-GPU workload (7 views, 1056x1920, D=64/32/8).  With --full the other shapes print a full "
+                         "line (roofline with that shape's algorithmic bytes, parity against the oracle on a down-scaled twin) without the CPU timing / side passes.")
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: ~1 s of cascade forwards: 600 at the default shape)")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train-step", action="store_true", help="skip the short config-3 training-iteration timing appended to the default line")
-    ap.add_argument("--no-side-pass", action="store_true", help="skip the side pass of the cascade workload (N = 1): two worker processes on the GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all: a fixed "
+                         "seeded sample of larger outputs); rank 0")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: rooflines from separate event-timed passes, the CPU "
+                         "baseline and parity against the oracle, the two-process side pass, the training-iteration appendix, per-rank rates")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity")
+    ap.add_argument("--no-train-step", action="store_true", help="with --full: skip the short config-3 training-iteration timing appended to the line")
+    ap.add_argument("--no-side-pass", action="store_true", help="with --full: skip the side pass of the cascade workload (N = 1): two worker processes on the GPU")
     ap.add_argument("--cpu-scenes", type=int, default=5, help="scenes timed on the CPU baseline after 2 warm-ups (bounded sample, BASELINE.md section 3)")
     args = ap.parse_args(argv)
     if args.gpus < 1 or args.procs_per_gpu < 1:
@@ -496,6 +536,8 @@ def main(argv=None):
     default_steps = args.steps is None
     if default_steps:
         args.steps = SHAPES[args.shape]["steps"] if args.workload == "cascade" else 600
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.shape != "dtu_bench":
         if args.workload != "cascade":
             ap.error("--shape applies to the cascade workload")
@@ -566,20 +608,25 @@ def main(argv=None):
         imgs, pm, dv = synthetic.cascade_inputs(1, V, H, W, seed)
         scenes.append((imgs.to(dev), {k: v.to(dev) for k, v in pm.items()}, dv.to(dev)))
 
+    last = {}
+
     def step(i):                                              # one CascadeMVSNet_eval.forward at batch 1 on the current stream
-        return model(*scenes[(i + rank) % len(scenes)])
+        last["out"] = model(*scenes[(i + rank) % len(scenes)])
 
     cdev = dev if args.procs_per_gpu == 1 else torch.device("cpu")      # where the rendezvous tensors live (RCCL / gloo)
     with torch.no_grad():
         for i in range(args.warmup):
-            out = step(i)
+            step(i)
         torch.cuda.synchronize()
-        elapsed, own, rounds = timed_rounds(world, cdev, args.steps, step, torch.cuda.synchronize)
-    # second, UNTIMED pass over the same scenes with HIP events (torch's current stream = the launch stream) around every K1 launch and
+        elapsed, own = timed_steps(world, cdev, args.steps, step, torch.cuda.synchronize)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last["out"])          # before any other pass reuses the model
+    # --full: second, UNTIMED pass over the same scenes with HIP events (torch's current stream = the launch stream) around every K1 launch and
     # every 3-D convolution launch: ~90 event records per scene would perturb `value` inside the timed region
     events, conv_events, smooth_events = [], [], []
     nprobe = min(10, args.steps)
-    if rank == 0:
+    sd1 = model1 = None
+    if rank == 0 and args.full:
         with torch.no_grad():
             ops.K1_EVENTS, ops.CONV_EVENTS = events, conv_events
             for i in range(nprobe):
@@ -587,7 +634,6 @@ def main(argv=None):
             torch.cuda.synchronize()
             ops.K1_EVENTS = ops.CONV_EVENTS = None
             # the smooth-head twin of the scene (prob.weight x1 instead of BASELINE.md's x20): K1 on depth maps that are not noise
-            sd1 = model1 = None
             if world == 1:
                 sd1 = synthetic.cascade_state_dict(0, prob_gain=1.0)
                 model1 = make_model(sd1)
@@ -600,11 +646,11 @@ def main(argv=None):
                 torch.cuda.synchronize()
                 ops.K1_EVENTS = None
 
-    # SIDE PASS (N = 1, one process; never `value`).  two_procs_per_gpu: the same workload as `python bench.py --procs-per-gpu 2` in a
+    # --full: SIDE PASS (N = 1, one process; never `value`).  two_procs_per_gpu: the same workload as `python bench.py --procs-per-gpu 2` in a
     # child -- two worker processes on this GPU, each issuing whole scenes on its own queue from its own address space (the item list is
     # sharded over the processes like over GPUs: rc_mvsnet_amd/sharding.py, eval_driver --procs-per-gpu)
     two_procs = None
-    if rank == 0 and world == 1 and not args.no_side_pass:
+    if rank == 0 and world == 1 and args.full and not args.no_side_pass:
         try:
             two_procs = two_procs_side_pass(min(300, max(20, args.steps)))
         except Exception as e:                               # never at the expense of the headline line
@@ -612,14 +658,46 @@ def main(argv=None):
 
     rank_rates = None
     if world > 1:
-        mine = torch.tensor([own], device=cdev, dtype=torch.float64)
-        every = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(every, mine)                        # every rank's own time of the median round: per-rank scenes/s (min / max) in the line
-        rank_rates = [args.steps / float(t.item()) for t in every]
+        if args.full:
+            mine = torch.tensor([own], device=cdev, dtype=torch.float64)
+            every = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(every, mine)                    # every rank's own time of the timed steps: per-rank scenes/s (min / max) in the line
+            rank_rates = [args.steps / float(t.item()) for t in every]
         dist.barrier()
         dist.destroy_process_group()                         # before rank 0 spends ~25 s on the CPU baseline alone
 
     if rank != 0:
+        return
+
+    result = {
+        "metric": SHAPES[args.shape]["metric"],
+        "value": round(world * args.steps / elapsed, 3),
+        "unit": "ref-scenes/s",
+        "n_gpus": args.gpus,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "timed_region_s": round(elapsed, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": SHAPES[args.shape]["workload"], "shape": args.shape,
+                   "views": V, "height": H, "width": W, "ndepths": list(NDEPTHS),
+                   "parallelism": f"scene-per-gpu x{args.gpus}" + (f", {args.procs_per_gpu} worker processes per GPU" if args.procs_per_gpu > 1 else ""),
+                   "ranks": world, "procs_per_gpu": args.procs_per_gpu,
+                   "rccl_ranks": world if (world > 1 and args.procs_per_gpu == 1) else 0},
+        # the scene as a whole against HBM: what every layer must move at least (K1 + the 3-D CNN's ideal activation traffic + the
+        # depth head + FeatureNet's maps, SURVEY.md section 8d) over the wall time of a step -- the honest summary next to the
+        # per-kernel objects: the scene is bound by its kernels' tick structures and launch latencies, not by a pipe
+        "roofline_scene": {"bound": "hbm", "algorithmic_bytes_per_scene": SCENE_ALGORITHMIC_BYTES,
+                           "achieved": round(SCENE_ALGORITHMIC_BYTES / (elapsed / args.steps) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(SCENE_ALGORITHMIC_BYTES / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
+                           "parts_MB": SCENE_PARTS_MB},
+    }
+    if not args.full:
+        print(json.dumps(result), flush=True)
         return
 
     # ---- roofline of K1 from the events of the probe pass -------------------------------------
@@ -677,38 +755,8 @@ def main(argv=None):
                                     "note": "same inputs and weights with prob.weight x1 instead of BASELINE.md's x20: stage-2 / 3 depth maps that are not "
                                             "noise, i.e. the gather locality of a trained network (the x20 scene's neighbouring pixels sample +-20 px apart)"}
 
-    roofline_conv = conv_roofline(conv_events, min(10, args.steps))
-
-    result = {
-        "metric": SHAPES[args.shape]["metric"],
-        "value": round(world * args.steps / elapsed, 3),
-        "unit": "ref-scenes/s",
-        "n_gpus": args.gpus,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "timed_region_s": round(elapsed, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": SHAPES[args.shape]["workload"], "shape": args.shape,
-                   "views": V, "height": H, "width": W, "ndepths": list(NDEPTHS),
-                   "parallelism": f"scene-per-gpu x{args.gpus}" + (f", {args.procs_per_gpu} worker processes per GPU" if args.procs_per_gpu > 1 else ""),
-                   "ranks": world, "procs_per_gpu": args.procs_per_gpu,
-                   "rccl_ranks": world if (world > 1 and args.procs_per_gpu == 1) else 0},
-        "roofline": roofline,
-        "roofline_conv": roofline_conv,
-        # the scene as a whole against HBM: what every layer must move at least (K1 + the 3-D CNN's ideal activation traffic + the
-        # depth head + FeatureNet's maps, SURVEY.md section 8d) over the wall time of a step -- the honest summary next to the
-        # per-kernel objects: the scene is bound by its kernels' tick structures and launch latencies, not by a pipe
-        "roofline_scene": {"bound": "hbm", "algorithmic_bytes_per_scene": SCENE_ALGORITHMIC_BYTES,
-                           "achieved": round(SCENE_ALGORITHMIC_BYTES / (elapsed / args.steps) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                           "frac": round(SCENE_ALGORITHMIC_BYTES / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
-                           "parts_MB": SCENE_PARTS_MB},
-    }
-    result.update(rounds_fields(rounds))
+    result["roofline"] = roofline
+    result["roofline_conv"] = conv_roofline(conv_events, min(10, args.steps))
     if two_procs is not None:
         result["two_procs_per_gpu"] = two_procs
     if rank_rates:

@@ -13,6 +13,7 @@ def main():
     captured = {}
     orig = bench.time.perf_counter
     args = A(); args.steps, args.warmup, args.gpus, args.no_cpu_baseline = 1, 2, 1, True
+    args.full, args.dump_outputs = False, None
     # reuse bench_train_step's set-up by running it with the profiler around its timed call
     import rc_mvsnet_amd.train_step as ts
     real = ts.train_step
