@@ -274,3 +274,187 @@ def test_render_forward_full_size_properties(hip):
     assert float(wts.sum(1).max()) <= 1.0 + 1e-4
     assert float(alpha.min()) >= 0.0 and float(alpha.max()) <= 1.0
     assert float(rgb.min()) >= 0.0 and float(rgb.max()) <= 1.0 + 1e-4
+
+
+# ------------------------------------------------------------------------------------------------
+# backward kernels of the rendering tail, each against fp64 autograd of the operation it differentiates (same fp32 inputs)
+# ------------------------------------------------------------------------------------------------
+def _per_ray_err(got, ref, floor=None):
+    """max over rays of max |got - ref| / (that ray's largest |ref|, at least `floor` (N,) and 1e-6: rays whose whole gradient is
+    below 1e-6 with O(1) inputs and cotangents -- samples behind a saturated one, a lone saturated sample -- are measured against 1e-6)."""
+    n = ref.shape[0]
+    d = (got.double() - ref).abs().reshape(n, -1).max(1).values
+    s = ref.abs().reshape(n, -1).max(1).values.clamp_min(1e-6)
+    if floor is not None:
+        s = torch.maximum(s, floor.double())
+    return float((d / s).max())
+
+
+def _composite_raw(N, S, regime, gen):
+    raw = torch.rand(N, S, 4, generator=gen)
+    if regime == "zero":                                   # alpha = 0 everywhere, T = 1
+        raw[..., 3] = 0.0
+    elif regime == "saturated":                            # alpha == 1.0f mid-ray: T drops to the 1e-10 floor (then 1e-20) behind it
+        raw[..., 3] = 0.05 * torch.rand(N, S, generator=gen)
+        raw[:, S // 2, 3] = 50.0
+        if S > 3:
+            raw[:, S // 2 + 1, 3] = 60.0
+    else:                                                  # mixed: empty, soft and saturated samples on every ray
+        raw[..., 3] = torch.relu(torch.randn(N, S, generator=gen)) * 0.5
+        raw[..., 3] = torch.where(torch.rand(N, S, generator=gen) < 0.02, torch.full((N, S), 40.0), raw[..., 3])
+    z = torch.sort(425 + 500 * torch.rand(N, S, generator=gen), dim=1).values
+    return raw, z
+
+
+def _composite_grads_fp64(raw, z, cot):
+    """d/d raw of sum(out_k * cot_k) over the oracle's fp64 compositing; cot = (g_rgb, g_depth, g_w, g_alpha), entries may be None."""
+    from oracle import render as orr
+    r = raw.detach().double().requires_grad_(True)
+    ref = orr.composite(r, z.double())
+    loss = r.new_zeros(())
+    for key, g in zip(("rgb_map", "depth_map", "weights", "alpha"), cot):
+        if g is not None:
+            loss = loss + (ref[key] * g.double()).sum()
+    loss.backward()
+    return r.grad
+
+
+# fp32 recurrences over S samples (T products, the reverse Q sum): the error grows with S (measured ~1e-6 at S = 1000)
+_COMPOSITE_TOL = 2e-5
+
+
+@pytest.mark.parametrize("N,S", [(1, 1), (63, 2), (65, 64), (70, 128), (5, 200), (3, 1000)])
+@pytest.mark.parametrize("regime", ["zero", "saturated", "mixed"])
+def test_composite_backward_vs_fp64_autograd(hip, N, S, regime):
+    """rcmvs_composite_bwd (one thread per ray, forward T pass + division-free reverse recurrence) through CompositeFn with all four
+    cotangents, and called directly with ONE cotangent and null pointers for the other three (autograd always materialises zeros,
+    so only a direct call reaches the null branches): against fp64 autograd of oracle.render.composite, per ray."""
+    from rc_mvsnet_amd import _lib, train_ops
+    gen = torch.Generator().manual_seed(N * 7 + S)
+    raw, z = _composite_raw(N, S, regime, gen)
+    cot = (torch.randn(N, 3, generator=gen), torch.randn(N, generator=gen) / 1000.0, torch.randn(N, S, generator=gen),
+           torch.randn(N, S, generator=gen))
+    # G_i - Q_i of the reverse recurrence cancels fp32 terms of size |g_depth| z (z = 425 ... 925) however close the samples are:
+    # that size is the yardstick of a ray as well
+    floor = cot[1].abs() * z.max(1).values
+    ref = _composite_grads_fp64(raw, z, cot)
+    rg = gpu(raw.clone()).requires_grad_(True)
+    outs = train_ops.CompositeFn.apply(rg, gpu(z))
+    sum((o * gpu(g)).sum() for o, g in zip(outs, cot)).backward()
+    err = _per_ray_err(rg.grad.cpu(), ref, floor)
+    assert err < _COMPOSITE_TOL, ("all four", err)
+    for k in range(4):
+        one = tuple(g if i == k else None for i, g in enumerate(cot))
+        ref_k = _composite_grads_fp64(raw, z, one)
+        r, zz = gpu(raw), gpu(z)
+        gs = [None if g is None else gpu(g) for g in one]
+        graw = torch.full_like(r, 7.0)                                  # every element must be written
+        _lib.check(_lib.load().rcmvs_composite_bwd(train_ops._chk(r, "raw"), train_ops._chk(zz, "z"), *(train_ops._opt(g, "g") for g in gs),
+                                                   train_ops._chk(graw, "grad_raw"), N, S, train_ops._stream()), "composite_bwd")
+        err = _per_ray_err(graw.cpu(), ref_k, floor if k == 1 else None)
+        assert err < _COMPOSITE_TOL, (("g_rgb", "g_depth", "g_w", "g_alpha")[k], err)
+
+
+def _grid_sample_fp64(vol_cl, ndc, gfeat8=None):
+    """trilinear grid_sample (zeros padding, align_corners=True) of the channels-last (Dv,hv,wv,8) volume at ndc*2-1 in fp64:
+    -> (values (M,8), d/d volume (Dv,hv,wv,8) of sum(values * gfeat8))."""
+    import torch.nn.functional as F
+    v = vol_cl.detach().double().permute(3, 0, 1, 2).unsqueeze(0).requires_grad_(True)          # (1,8,Dv,hv,wv)
+    grid = (ndc.double() * 2.0 - 1.0).reshape(1, 1, 1, -1, 3)                          # x -> wv, y -> hv, z -> Dv
+    out = F.grid_sample(v, grid, mode="bilinear", padding_mode="zeros", align_corners=True)[0, :, 0, 0].t()   # (M,8)
+    if gfeat8 is None:
+        return out.detach(), None
+    (out * gfeat8.double()).sum().backward()
+    return out.detach(), v.grad[0].permute(1, 2, 3, 0)
+
+
+def _lattice_points(Dv, hv, wv, gen):
+    """points exactly on lattice nodes (ndc = k/(n-1), the far faces at 1.0), on lattice edges (two coordinates on nodes) and faces."""
+    node = lambda n: torch.arange(n, dtype=torch.float32) / max(n - 1, 1)
+    gz, gy, gx = torch.meshgrid(node(Dv), node(hv), node(wv), indexing="ij")
+    nodes = torch.stack((gx, gy, gz), -1).reshape(-1, 3)
+    edges = nodes[torch.randint(0, nodes.shape[0], (300,), generator=gen)].clone()
+    axis = torch.randint(0, 3, (300,), generator=gen)
+    edges[torch.arange(300), axis] = torch.rand(300, generator=gen)
+    face = torch.rand(200, 3, generator=gen)
+    face[:100, 0] = 1.0
+    face[100:, 2] = 1.0
+    return torch.cat((nodes, edges, face, torch.ones(1, 3), torch.zeros(1, 3)))
+
+
+@pytest.mark.parametrize("case", ["spread", "lattice", "Dv1", "hv1", "wv1", "collide"])
+def test_point_feats_backward_vs_fp64_grid_sample(hip, case):
+    """rcmvs_point_feats_bwd (trilinear scatter with hardware fp32 atomics) through PointFeatsFn, and its forward columns 0-7, against
+    fp64 F.grid_sample: points inside and outside the volume, exactly on nodes / edges / far faces, degenerate one-voxel-thick volumes,
+    M not a multiple of 256, and thousands of points colliding in a 2x2x2 volume.  Gradient columns >= 8 (image taps, masks, padding)
+    carry large values that must not reach the volume."""
+    from rc_mvsnet_amd import train_ops
+    gen = torch.Generator().manual_seed(len(case))
+    dims = {"spread": (7, 9, 13), "lattice": (5, 6, 7), "Dv1": (1, 9, 13), "hv1": (7, 1, 13), "wv1": (7, 9, 1), "collide": (2, 2, 2)}[case]
+    Dv, hv, wv = dims
+    if case == "lattice":
+        ndc = _lattice_points(Dv, hv, wv, gen)
+    elif case == "collide":
+        ndc = torch.cat((torch.rand(5000, 3, generator=gen), -0.2 + 1.4 * torch.rand(123, 3, generator=gen)))
+    else:
+        ndc = -0.2 + 1.4 * torch.rand(1000, 3, generator=gen)
+    M = ndc.shape[0]
+    assert M % 256
+    ldf = 16
+    vol = torch.randn(Dv, hv, wv, 8, generator=gen)
+    gfeat = torch.randn(M, ldf, generator=gen)
+    gfeat[:, 8:] *= 1e3
+    imgs = torch.rand(1, 3, 4, 5, generator=gen)
+    poses = torch.cat((torch.eye(4).reshape(16), torch.eye(3).reshape(9))).reshape(1, 25)
+    pts = torch.rand(M, 1, 3, generator=gen) + torch.tensor([0.0, 0.0, 1.0])
+    want, gref = _grid_sample_fp64(vol, ndc, gfeat[:, :8])
+    vg = gpu(vol.clone()).requires_grad_(True)
+    feat = train_ops.PointFeatsFn.apply(vg, gpu(imgs), gpu(poses), gpu(pts), gpu(ndc.reshape(M, 1, 3)), ldf)
+    (feat * gpu(gfeat)).sum().backward()
+    got = vg.grad.cpu().double()
+    # forward: fp32 coordinates move each trilinear weight by <= ~4 ulp x (n - 1) (n <= 13 voxels per axis): < 1e-5 of the values
+    assert float((feat.detach().cpu()[:, :8].double() - want).abs().max()) < 1e-5 * float(want.abs().max())
+    if case != "collide":
+        assert float((got - gref).abs().max()) < 1e-5 * float(gref.abs().max())
+    else:
+        # every point of the unit cube adds to all 8 voxels: n = M fp32 additions per (voxel, channel), in whatever order the atomics
+        # land.  Bound: (n + 3) u sum|g w| (summation + the products g * ((wx wy) wz)) + 4 u sum|g| (the fp32 coordinate moves each
+        # weight by <= 4 u here, n - 1 = 1), u = 2^-24
+        u = 2.0 ** -24
+        _, gabs = _grid_sample_fp64(vol, ndc, gfeat[:, :8].abs())
+        bound = (M + 3) * u * gabs + 4 * u * gfeat[:, :8].abs().double().sum(0)
+        excess = float(((got - gref).abs() - bound).max())
+        assert excess <= 0.0, excess
+
+
+@pytest.mark.parametrize("C,Cp", [(41, 44), (60, 60)])
+@pytest.mark.parametrize("D,Do", [(48, 128), (12, 128), (127, 128), (128, 127), (9, 9), (20, 7), (1, 9), (1, 1), (5, 1)])
+def test_resize_planes_forward_backward_vs_fp64(hip, C, Cp, D, Do):
+    """ResizePlanesFn: forward (rcmvs_resize_planes_fwd) and its exact adjoint (rcmvs_resize_planes_bwd: klo/khi window of the output
+    planes that read input plane j) against fp64 F.interpolate(trilinear, align_corners=True, size=[Do,h,w]) and its autograd: batch
+    2, h*w = 279 (above 256, not a multiple), padding columns of the cotangent nonzero (they must not leak).  Do = 1 is accepted and
+    matches torch (align_corners with one output sample reads plane 0)."""
+    import torch.nn.functional as F
+    from rc_mvsnet_amd import train_ops
+    gen = torch.Generator().manual_seed(D * 131 + Do + C)
+    B, h, w = 2, 9, 31
+    x = torch.randn(B, C, D, h, w, generator=gen)
+    G = torch.randn(B, Do, h, w, Cp, generator=gen)
+    xr = x.double().requires_grad_(True)
+    ref = F.interpolate(xr, size=[Do, h, w], mode="trilinear", align_corners=True)
+    (ref * G[..., :C].double().permute(0, 4, 1, 2, 3)).sum().backward()
+    xg = gpu(x.clone()).requires_grad_(True)
+    y = train_ops.ResizePlanesFn.apply(xg, Do, Cp)
+    assert tuple(y.shape) == (B, Do, h, w, Cp)
+    (y * gpu(G)).sum().backward()
+    yc = y.detach().cpu()
+    if Cp > C:
+        assert float(yc[..., C:].abs().max()) == 0.0
+    # the fp32 source coordinate scale * k is off by <= 2u (D - 1) (u = 2^-24), and so are the lerp weights: forward within
+    # 4u D max|x|; an input plane gathers n <= 2 ceil((Do - 1) / (D - 1)) + 2 weighted cotangents (n = Do when D = 1), each weight
+    # off by as much, plus n roundings of the sum: backward within n (2D + n) u max|G|
+    u = 2.0 ** -24
+    assert float((yc[..., :C].permute(0, 4, 1, 2, 3).double() - ref.detach()).abs().max()) <= 4 * u * D * float(x.abs().max())
+    n = Do if D == 1 else 2 * -(-(Do - 1) // (D - 1)) + 2
+    gx = xg.grad.cpu().double()
+    assert float((gx - xr.grad).abs().max()) <= n * (2 * D + n) * u * float(G[..., :C].abs().max())

@@ -96,15 +96,20 @@ def test_conv_bn_relu_block_forward_backward(ci, co, stride, transposed, relu, w
     assert max(errs.values()) < 1e-4
 
 
-def test_prob_depth_head_backward():
+@pytest.mark.parametrize("D", [8, 32, 48])
+@pytest.mark.parametrize("h,w", [(16, 24), (13, 37), (5, 70)])
+@pytest.mark.parametrize("gain", [1.0, 8.0])
+def test_prob_depth_head_backward(D, h, w, gain):
+    """ProbDepthHeadFn backward: rcmvs_depth_head_bwd (softmax / soft-argmin), rcmvs_conv3d_dgrad_c1 (dx) and the prob marching wgrad
+    (dw) against fp64 autograd at the training depths D = 48 / 32 / 8, ragged maps, a flat softmax and a saturated one (gain x8)."""
     import torch.nn.functional as F
     from rc_mvsnet_amd import _lib, train_ops
     _lib.load()
     dev = DEV
-    g = torch.Generator().manual_seed(5)
-    B, D, h, w = 2, 8, 16, 24
+    g = torch.Generator().manual_seed(5 + D + h + int(gain))
+    B = 2
     x8 = torch.randn(B, 8, D, h, w, generator=g)
-    wp = torch.randn(1, 8, 3, 3, 3, generator=g) * 0.3
+    wp = torch.randn(1, 8, 3, 3, 3, generator=g) * (0.3 * gain)
     planes = torch.stack((450 + 100 * torch.rand(B, h, w, generator=g), 2.0 + torch.rand(B, h, w, generator=g)), dim=-1)
     G = torch.randn(B, h, w, generator=g)
     xr, wr = x8.double().requires_grad_(True), wp.double().requires_grad_(True)
@@ -164,6 +169,163 @@ def test_conv3d_weight_gradient_cout8_paired_columns(Ci, shape):
         assert float(w.grad[:, :, 0].abs().max()) == 0.0 and float(w.grad[:, :, 2].abs().max()) == 0.0
     err = float((dw.double() - ref).abs().max() / ref.abs().max())
     assert err < 2e-5, err
+
+
+# every (Ci, Co, stride) entry of rcmvs_conv3d_wgrad's dispatch table (the 8 -> 1 prob layer included); the stride-2 entries in both roles
+# (forward conv, and the transposed conv whose roles _conv_wgrad swaps); the sliced Co = 8 path for other input widths (32 + 16 + 8 + 4)
+_WGRAD_TABLE = [(8, 1, 1), (8, 8, 1), (16, 8, 1), (32, 8, 1), (16, 16, 1), (32, 32, 1), (64, 64, 1),
+                (32, 16, 1), (64, 32, 1), (16, 32, 1), (8, 32, 1), (8, 16, 2), (16, 32, 2), (32, 64, 2)]
+_WGRAD_CASES = ([(p, q, s, False) for p, q, s in _WGRAD_TABLE] + [(p, q, 2, True) for p, q, s in _WGRAD_TABLE if s == 2] +
+                [(p, 8, 1, False) for p in (12, 20, 36, 44, 60)])
+
+
+def _wgrad_vs_fp64(P, Q, stride, transposed, big_shape, g):
+    """(got twice through _wgrad_to_param_layout, fp64 reference) for a layer whose large tensor has P channels and shape big_shape
+    (B, D, H, W) and whose small one has Q; transposed: ConvTranspose3d(Q -> P, stride 2) with weight (Q, P, 3, 3, 3)."""
+    import torch.nn.functional as F
+    from rc_mvsnet_amd import train_ops
+    B, D, H, W = big_shape
+    small = (B, (D - 1) // stride + 1, (H - 1) // stride + 1, (W - 1) // stride + 1)
+    big = torch.randn(B, P, D, H, W, generator=g)
+    sm = torch.randn(B, Q, *small[1:], generator=g)
+    w = torch.zeros(Q, P, 3, 3, 3, dtype=torch.float64, requires_grad=True)
+    if transposed:              # x = sm (Q channels), y = big (P channels, cotangent)
+        (F.conv_transpose3d(sm.double(), w, stride=2, padding=1, output_padding=1) * big.double()).sum().backward()
+    else:                       # x = big, y = sm (cotangent)
+        (F.conv3d(big.double(), w, stride=stride, padding=1) * sm.double()).sum().backward()
+    cl = lambda t: t.permute(0, 2, 3, 4, 1).contiguous().to(DEV)
+    got = [train_ops._wgrad_to_param_layout(cl(big), cl(sm), stride, (Q, P, 3, 3, 3)).cpu() for _ in range(2)]
+    return got, w.grad
+
+
+@pytest.mark.parametrize("P,Q,stride,transposed", _WGRAD_CASES)
+def test_conv3d_weight_gradient_every_dispatch_branch(P, Q, stride, transposed):
+    """rcmvs_conv3d_wgrad through _wgrad_to_param_layout (persistent packed buffer + rcmvs_wgrad_finish), twice in a row, against fp64
+    autograd of conv3d / conv_transpose3d: batch 2, ragged H and W.  The second call accumulates into the buffer the first one's
+    finish cleared."""
+    g = torch.Generator().manual_seed(P * 97 + Q * 3 + stride + int(transposed))
+    big_shape = (2, 4, 10, 22) if transposed else (2, 3, 7, 13)
+    got, ref = _wgrad_vs_fp64(P, Q, stride, transposed, big_shape, g)
+    for dw in got:
+        assert tuple(dw.shape) == tuple(ref.shape)
+        err = _rel(dw, ref)
+        assert err < 2e-5, err
+
+
+@pytest.mark.parametrize("P,Q", [(32, 16), (64, 32), (16, 32), (8, 32), (32, 8), (44, 8)])
+@pytest.mark.parametrize("W", [129, 300, 640])
+def test_conv3d_weight_gradient_one_plane_w_split(P, Q, W):
+    """One-plane volumes (D = 1, FeatureNet's layers) with Wo >= 128: the wgrad launch splits every row into w chunks over grid.z
+    (chunk widths rounded up to 4 cells; 129 and 300 leave a ragged last chunk).  Against fp64 conv3d, batch 2, through the
+    parameter-layout path twice."""
+    g = torch.Generator().manual_seed(P + Q + W)
+    got, ref = _wgrad_vs_fp64(P, Q, 1, False, (2, 1, 3, W), g)
+    assert float(ref[:, :, 0].abs().max()) == 0.0 and float(ref[:, :, 2].abs().max()) == 0.0      # padding planes only
+    for dw in got:
+        err = _rel(dw, ref)
+        assert err < 2e-5, err
+
+
+def _bn_ref(y, gamma, beta, relu):
+    import torch.nn.functional as F
+    z = F.batch_norm(y, None, None, gamma, beta, training=True, eps=1e-5)
+    return F.relu(z) if relu else z
+
+
+def test_conv_bn_block_with_padded_input_channels():
+    """The renderer's first CostReg layer: 41 real input channels carried as 44 (zero channels 41-43), Conv3d 41 -> 8, stride 1,
+    batch-statistics norm, no ReLU.  Its backward takes the _conv_dgrad branch that pads the weight to 48 adjoint outputs and crops
+    back to 44, and the sliced wgrad path (32 + 8 + 4).  z, dx, dw, dgamma, dbeta and the running statistics against fp64; dx in the
+    padding channels exactly 0."""
+    import torch.nn.functional as F
+    from rc_mvsnet_amd import _lib, train_ops
+    _lib.load()
+    g = torch.Generator().manual_seed(41)
+    B, D, H, W = 2, 5, 6, 11
+    x = torch.randn(B, 41, D, H, W, generator=g)
+    w = torch.randn(8, 41, 3, 3, 3, generator=g) / (27 * 41) ** 0.5
+    gamma, beta = 0.5 + torch.rand(8, generator=g), 0.2 * torch.randn(8, generator=g)
+    G = torch.randn(B, 8, D, H, W, generator=g)
+    xr, wr, gr, br = (t.double().requires_grad_(True) for t in (x, w, gamma, beta))
+    yr = F.conv3d(xr, wr, padding=1)
+    zr = _bn_ref(yr, gr, br, False)
+    (zr * G.double()).sum().backward()
+    x44 = F.pad(x.permute(0, 2, 3, 4, 1), (0, 3)).contiguous()
+    xg = x44.to(DEV).requires_grad_(True)
+    wg, gg, bg = (t.clone().to(DEV).requires_grad_(True) for t in (w, gamma, beta))
+    rm, rv = torch.zeros(8, device=DEV), torch.ones(8, device=DEV)
+    cfg = {"transposed": False, "stride": 1, "relu": False, "eps": 1e-5, "momentum": 0.1, "group": None}
+    z = train_ops.ConvBnReluFn.apply(xg, wg, gg, bg, None, rm, rv, cfg)
+    (z * G.permute(0, 2, 3, 4, 1).to(DEV)).sum().backward()
+    dx = xg.grad.cpu()
+    assert dx.shape == (B, D, H, W, 44) and float(dx[..., 41:].abs().max()) == 0.0
+    yd = yr.detach()
+    assert _rel(z.detach().cpu().permute(0, 4, 1, 2, 3), zr.detach()) < 2e-5
+    assert float((rm.cpu() - 0.1 * yd.mean(dim=(0, 2, 3, 4))).abs().max()) < 1e-5
+    assert _rel(rv.cpu(), 0.9 + 0.1 * yd.var(dim=(0, 2, 3, 4), unbiased=True)) < 2e-5
+    errs = {"dx": _rel(dx[..., :41].permute(0, 4, 1, 2, 3), xr.grad), "dw": _rel(wg.grad.cpu(), wr.grad),
+            "dgamma": _rel(gg.grad.cpu(), gr.grad), "dbeta": _rel(bg.grad.cpu(), br.grad)}
+    print("41-in-44 block: " + " ".join(f"{k}={v:.1e}" for k, v in errs.items()))
+    assert max(errs.values()) < 1e-4, errs             # the bound of test_conv_bn_relu_block_forward_backward
+
+
+@pytest.mark.parametrize("ci,co", [(32, 8), (16, 32), (8, 32)])
+def test_conv_plain_block_with_bias_one_plane(ci, co):
+    """ConvPlainFn with bias on a one-plane volume (FeatureNet's out / inner layers, W >= 128 so the weight gradient splits rows): y, dx,
+    dw and db against fp64 conv3d."""
+    import torch.nn.functional as F
+    from rc_mvsnet_amd import _lib, train_ops
+    _lib.load()
+    g = torch.Generator().manual_seed(ci * 10 + co)
+    B, H, W = 2, 6, 160
+    x = torch.randn(B, ci, 1, H, W, generator=g)
+    w = torch.randn(co, ci, 3, 3, 3, generator=g) / (9 * ci) ** 0.5
+    b = torch.randn(co, generator=g)
+    G = torch.randn(B, co, 1, H, W, generator=g)
+    xr, wr, br = (t.double().requires_grad_(True) for t in (x, w, b))
+    yr = F.conv3d(xr, wr, br, padding=1)
+    (yr * G.double()).sum().backward()
+    xg = x.permute(0, 2, 3, 4, 1).contiguous().to(DEV).requires_grad_(True)
+    wg, bg = w.clone().to(DEV).requires_grad_(True), b.clone().to(DEV).requires_grad_(True)
+    y = train_ops.ConvPlainFn.apply(xg, wg, bg)
+    (y * G.permute(0, 2, 3, 4, 1).to(DEV)).sum().backward()
+    errs = {"y": _rel(y.detach().cpu().permute(0, 4, 1, 2, 3), yr.detach()), "dx": _rel(xg.grad.cpu().permute(0, 4, 1, 2, 3), xr.grad),
+            "dw": _rel(wg.grad.cpu(), wr.grad), "db": _rel(bg.grad.cpu(), br.grad)}
+    print(f"plain {ci}->{co}: " + " ".join(f"{k}={v:.1e}" for k, v in errs.items()))
+    assert max(errs.values()) < 2e-5, errs
+
+
+def test_conv_bn_block_two_segments_vs_two_batchnorm_calls():
+    """ConvBnReluFn with segments = 2 (FeatureNet's per-view statistics): one convolution over both images, each image normalised with
+    its own batch statistics and the running statistics updated once per segment, in order -- against two separate fp64 batch-norm
+    calls: outputs, all gradients and the running statistics."""
+    import torch.nn.functional as F
+    from rc_mvsnet_amd import _lib, train_ops
+    _lib.load()
+    g = torch.Generator().manual_seed(22)
+    B, H, W, ci, co = 2, 12, 40, 8, 8
+    x = torch.randn(B, ci, 1, H, W, generator=g)
+    x[1] = 2.0 * x[1] + 0.5                                   # the two segments have different statistics
+    w = torch.randn(co, ci, 3, 3, 3, generator=g) / (9 * ci) ** 0.5
+    gamma, beta = 0.5 + torch.rand(co, generator=g), 0.2 * torch.randn(co, generator=g)
+    G = torch.randn(B, co, 1, H, W, generator=g)
+    rm0, rv0 = 0.1 * torch.randn(co, generator=g), 0.5 + torch.rand(co, generator=g)
+    xr, wr, gr, br = (t.double().requires_grad_(True) for t in (x, w, gamma, beta))
+    yr = F.conv3d(xr, wr, padding=1)
+    rmr, rvr = rm0.double(), rv0.double()
+    zr = torch.cat([F.relu(F.batch_norm(yr[i:i + 1], rmr, rvr, gr, br, training=True, momentum=0.1, eps=1e-5)) for i in range(2)])
+    (zr * G.double()).sum().backward()
+    xg = x.permute(0, 2, 3, 4, 1).contiguous().to(DEV).requires_grad_(True)
+    wg, gg, bg = (t.clone().to(DEV).requires_grad_(True) for t in (w, gamma, beta))
+    rm, rv = rm0.clone().to(DEV), rv0.clone().to(DEV)
+    cfg = {"transposed": False, "stride": 1, "relu": True, "eps": 1e-5, "momentum": 0.1, "group": None, "segments": 2}
+    z = train_ops.ConvBnReluFn.apply(xg, wg, gg, bg, None, rm, rv, cfg)
+    (z * G.permute(0, 2, 3, 4, 1).to(DEV)).sum().backward()
+    errs = {"z": _rel(z.detach().cpu().permute(0, 4, 1, 2, 3), zr.detach()), "dx": _rel(xg.grad.cpu().permute(0, 4, 1, 2, 3), xr.grad),
+            "dw": _rel(wg.grad.cpu(), wr.grad), "dgamma": _rel(gg.grad.cpu(), gr.grad), "dbeta": _rel(bg.grad.cpu(), br.grad),
+            "running_mean": _rel(rm.cpu(), rmr), "running_var": _rel(rv.cpu(), rvr)}
+    print("two segments: " + " ".join(f"{k}={v:.1e}" for k, v in errs.items()))
+    assert max(errs.values()) < 1e-4, errs             # the bound of test_conv_bn_relu_block_forward_backward
 
 
 def test_cascade_train_native_vs_delegated_gradients():
