@@ -529,6 +529,48 @@ int rcmvs_resize_rgb_cl(const float* x, float* y, int N, int H, int W, int h, in
 int rcmvs_prepare_image(const unsigned char* src, float* out, int H, int W, int h, int w, const float* mean_host,
                         const float* std_host, void* stream);
 
+/* ---- DTU point-cloud scorer (rc_mvsnet_amd/dtu_eval.py) -----------------------------------------------------------------
+ * Replaces matlab_eval/PointCompareMain.m (reducePts_haa.m, MaxDistCP.m, the ObsMask and ground-plane tests) and the per-scan
+ * statistics of ComputeStat_web_pt.m.  These entry points are additive: RCMVS_VERSION stays 106, and a caller checks for them
+ * by symbol.  Point clouds are (n,3) fp32, n below 2^31.  A uniform grid is described by two HOST arrays:
+ * grid_host = {origin x, y, z, cell edge h} (doubles), dims_host = {gx, gy, gz} (at most RCMVS_PC_MAX_CELLS cells);
+ * the cell of a point is clamp(floor((p - origin) / h), 0, g - 1) per axis, cells numbered x fastest. */
+#define RCMVS_PC_MAX_CELLS (1 << 24)
+#define RCMVS_PC_SCAN_TILE 2048      /* ints per block of the multi-block scan: a scan of m ints uses ceil(m / 2048) + 1 ints of work */
+#define RCMVS_PC_BBOX_BLOCKS 1024
+#define RCMVS_PC_MOMENT_BLOCKS 256
+/* pts (n,3) -> out[6] = {min x, y, z, max x, y, z}; part: 6 * RCMVS_PC_BBOX_BLOCKS floats of work. */
+int rcmvs_pc_bbox(const float* pts, long long n, float* part, float* out, void* stream);
+/* Counting sort of pts into the grid: key (n) and count (gx gy gz) ints of work, scan_work (ceil(cells / 2048) + 1) ints;
+ * cell_start (cells + 1) receives the first sorted slot of every cell, sorted (n,4) the points in cell order (w = 0) and
+ * sorted_idx (n) their input index.  The order inside a cell is unspecified. */
+int rcmvs_pc_grid_build(const float* pts, long long n, const double* grid_host, const int* dims_host, int* key, int* count,
+                        int* scan_work, int* cell_start, float* sorted, int* sorted_idx, void* stream);
+/* out[i] (double) = min(distance from q[i] to its nearest point of the grid's n_to points, cap), computed in fp64.
+ * lattice_host = NULL or {lo x, y, z, hi x, y, z} (doubles): a query outside [lo, hi) in some axis gets cap (MaxDistCP never
+ * visits it).  n_to = 0: every query gets cap (grid arguments unused). */
+int rcmvs_pc_nearest(const float* q, long long nq, const double* grid_host, const int* dims_host, const int* cell_start,
+                     const float* sorted, long long n_to, double cap, const double* lattice_host, double* out, void* stream);
+/* reducePts_haa's greedy in rounds over a grid whose cell edge is >= dst.  order (n) int64: a permutation, the visiting order;
+ * rank / sorted_rank (n) ints of work; init sets state (n) u8 to undecided.  A round reads s_in, writes s_out and ADDS the
+ * number of points left undecided to *undecided (zeroed by the call); the caller swaps the buffers and repeats until it reads 0.
+ * finish: kept (n) u8 = 1 where the point is kept, in input order. */
+int rcmvs_pc_reduce_init(const long long* order, const int* sorted_idx, long long n, int* rank, int* sorted_rank,
+                         unsigned char* state, void* stream);
+int rcmvs_pc_reduce_round(const double* grid_host, const int* dims_host, const int* cell_start, const float* sorted,
+                          const int* sorted_rank, const unsigned char* s_in, unsigned char* s_out, long long n, double dst,
+                          int* undecided, void* stream);
+int rcmvs_pc_reduce_finish(const unsigned char* state, const int* sorted_idx, long long n, unsigned char* kept, void* stream);
+/* flags (n) u8 = DataInMask (mode 0; params_host = {BB(1,:), Res}, obs_mask (s1,s2,s3) u8 column-major) or StlAbovePlane
+ * (mode 1; params_host = P, obs_mask unused); out receives d[i] of every point with flags[i] && d[i] < thresh, in point order.
+ * work: 2 ceil(n / 256) + 1 + ceil(ceil(n / 256) / 2048) + 1 ints; the count of out lands in work[2 ceil(n / 256)]. */
+int rcmvs_pc_select(const float* pts, const double* d, long long n, int mode, const double* params_host,
+                    const unsigned char* obs_mask, int s1, int s2, int s3, double thresh, unsigned char* flags,
+                    double* out, int* work, void* stream);
+/* stats[3] = {count, mean, variance (N - 1)} of x[0 .. *count) in fp64 (NaN for an empty set, variance 0 for one value);
+ * part: RCMVS_PC_MOMENT_BLOCKS doubles of work. */
+int rcmvs_pc_moments(const double* x, const int* count, double* part, double* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

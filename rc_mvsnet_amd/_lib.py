@@ -108,6 +108,15 @@ SIGNATURES = {
     "rcmvs_nerf_workspace_floats": [_ll],
     "rcmvs_pack_nerf_weights": [_p, _p, _p],
     "rcmvs_composite_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _p],
+    # DTU point-cloud scorer (additive entry points of version 106)
+    "rcmvs_pc_bbox": [_p, _ll, _p, _p, _p],
+    "rcmvs_pc_grid_build": [_p, _ll, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "rcmvs_pc_nearest": [_p, _ll, _p, _p, _p, _p, _ll, _d, _p, _p, _p],
+    "rcmvs_pc_reduce_init": [_p, _p, _ll, _p, _p, _p, _p],
+    "rcmvs_pc_reduce_round": [_p, _p, _p, _p, _p, _p, _p, _ll, _d, _p, _p],
+    "rcmvs_pc_reduce_finish": [_p, _p, _ll, _p, _p],
+    "rcmvs_pc_select": [_p, _p, _ll, _i, _p, _p, _i, _i, _i, _d, _p, _p, _p, _p],
+    "rcmvs_pc_moments": [_p, _p, _p, _p, _p],
 }
 _RESTYPES = {"rcmvs_last_error_string": ctypes.c_char_p, "rcmvs_nerf_weight_floats": _ll, "rcmvs_nerf_workspace_floats": _ll, "rcmvs_nerf_train_workspace_floats": _ll, "rcmvs_nerf_bwd_workspace_floats": _ll,
              "rcmvs_packed_weight_floats": _ll, "rcmvs_fpn_folded_mfma_floats": _ll, "rcmvs_conv2d_pair_weight_floats": _ll, "rcmvs_conv2d_stem_weight_floats": _ll, "rcmvs_conv2d_tile_weight_floats": _ll}

@@ -1,0 +1,185 @@
+"""Readers for the DTU scorer (rc_mvsnet_amd/dtu_eval.py): PLY vertex positions and MATLAB v5 .mat files.
+
+``read_ply_xyz``: ascii, binary_little_endian and binary_big_endian PLY, any scalar property types; returns the vertex element's
+x / y / z as (n,3) float32 and skips every other property and element (faces after the vertices included).  It reads what
+``fusion.ply_bytes`` writes and DTU's ``Points/stl/stl%03d_total.ply``.
+
+``read_mat``: the MAT-file level 5 format (uncompressed and zlib-compressed variables), full numeric and logical arrays only,
+so that scipy is not a runtime dependency.  Arrays come back in MATLAB's index order (``a[i-1, j-1, k-1]`` is ``A(i,j,k)``).
+Other classes (cell, struct, char, sparse, objects) are skipped.  v7.3 files (HDF5) are refused with a clear error.
+"""
+import struct
+import zlib
+
+import numpy as np
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+class FormatError(ValueError):
+    pass
+
+
+def _ply_header(f):
+    if f.readline().strip() != b"ply":
+        raise FormatError("not a PLY file")
+    fmt, elements = None, []
+    while True:
+        line = f.readline()
+        if not line:
+            raise FormatError("PLY header without end_header")
+        tok = line.decode("ascii", "replace").split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "end_header":
+            break
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property":
+            if not elements:
+                raise FormatError("PLY property before any element")
+            if tok[1] == "list":
+                elements[-1][2].append((tok[4], ("list", _ply_type(tok[2]), _ply_type(tok[3]))))
+            else:
+                elements[-1][2].append((tok[2], _ply_type(tok[1])))
+    if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+        raise FormatError(f"PLY format {fmt!r}")
+    return fmt, elements
+
+
+def _ply_type(name):
+    if name not in _PLY_TYPES:
+        raise FormatError(f"PLY property type {name!r}")
+    return _PLY_TYPES[name]
+
+
+def _skip_binary_element(f, count, props, end):
+    """Skip one binary element (list properties read item by item)."""
+    if all(not isinstance(t, tuple) for _, t in props):
+        f.seek(count * sum(np.dtype(t).itemsize for _, t in props), 1)
+        return
+    for _ in range(count):
+        for _, t in props:
+            if isinstance(t, tuple):
+                cdt = np.dtype(t[1]).newbyteorder(end)
+                k = int(np.frombuffer(f.read(cdt.itemsize), dtype=cdt)[0])
+                f.seek(k * np.dtype(t[2]).itemsize, 1)
+            else:
+                f.seek(np.dtype(t).itemsize, 1)
+
+
+def read_ply_xyz(path):
+    """-> (n,3) float32 vertex positions of a PLY file."""
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f)
+        names = [e[0] for e in elements]
+        if "vertex" not in names:
+            raise FormatError(f"{path}: no vertex element")
+        vprops = elements[names.index("vertex")][2]
+        pnames = [p for p, _ in vprops]
+        for k in ("x", "y", "z"):
+            if k not in pnames:
+                raise FormatError(f"{path}: vertex has no property {k}")
+        if any(isinstance(t, tuple) for _, t in vprops):
+            raise FormatError(f"{path}: list properties in the vertex element are not supported")
+        if fmt == "ascii":
+            lines = f.read().decode("ascii").splitlines()
+            row = 0
+            for name, count, props in elements:
+                if name == "vertex":
+                    rows = [ln.split() for ln in lines[row:row + count]]
+                    if len(rows) != count:
+                        raise FormatError(f"{path}: {len(rows)} of {count} vertices")
+                    cols = [pnames.index(k) for k in ("x", "y", "z")]
+                    return np.array([[float(r[c]) for c in cols] for r in rows], dtype=np.float64).astype(np.float32).reshape(count, 3)
+                row += count
+        end = "<" if fmt == "binary_little_endian" else ">"
+        for name, count, props in elements:
+            if name == "vertex":
+                dt = np.dtype([(p, np.dtype(t).newbyteorder(end)) for p, t in props])
+                buf = f.read(dt.itemsize * count)
+                if len(buf) != dt.itemsize * count:
+                    raise FormatError(f"{path}: truncated vertex data")
+                rec = np.frombuffer(buf, dtype=dt)
+                return np.stack([rec[k].astype(np.float32) for k in ("x", "y", "z")], axis=1)
+            _skip_binary_element(f, count, props, end)
+    raise FormatError(f"{path}: no vertex element")       # not reached
+
+
+# ---- MAT v5 --------------------------------------------------------------------------------------------------------------
+_MI = {1: "i1", 2: "u1", 3: "i2", 4: "u2", 5: "i4", 6: "u4", 7: "f4", 9: "f8", 12: "i8", 13: "u8"}
+_MX = {6: "f8", 7: "f4", 8: "i1", 9: "u1", 10: "i2", 11: "u2", 12: "i4", 13: "u4", 14: "i8", 15: "u8"}
+MI_MATRIX, MI_COMPRESSED = 14, 15
+
+
+def _elements(buf, end):
+    """Yield (type, payload bytes) of the data elements of buf."""
+    pos = 0
+    while pos + 8 <= len(buf):
+        first, second = struct.unpack(end + "II", buf[pos:pos + 8])
+        if first >> 16:                                        # small data element: 2-byte size, 2-byte type, 4 bytes of data
+            n, typ = first >> 16, first & 0xFFFF
+            yield typ, buf[pos + 4:pos + 4 + n]
+            pos += 8
+            continue
+        typ, n = first, second
+        payload = buf[pos + 8:pos + 8 + n]
+        if len(payload) != n:
+            raise FormatError("truncated MAT data element")
+        yield typ, payload
+        pos += 8 + n
+        if typ != MI_COMPRESSED:
+            pos += (-n) % 8
+
+
+def _numeric(typ, payload, end):
+    if typ not in _MI:
+        raise FormatError(f"MAT data type {typ}")
+    return np.frombuffer(payload, dtype=np.dtype(_MI[typ]).newbyteorder(end))
+
+
+def _matrix(payload, end):
+    """-> (name, array) of a miMATRIX element, or (name, None) for a class this reader skips."""
+    sub = list(_elements(payload, end))
+    if len(sub) < 3:
+        raise FormatError("malformed MAT matrix")
+    flags = _numeric(*sub[0], end)
+    cls, logical, cplx = int(flags[0]) & 0xFF, bool(int(flags[0]) & 0x200), bool(int(flags[0]) & 0x800)
+    dims = [int(d) for d in _numeric(*sub[1], end)]
+    name = bytes(sub[2][1]).decode("ascii", "replace")
+    if cls not in _MX or cplx:
+        return name, None
+    real = _numeric(*sub[3], end) if len(sub) > 3 else np.zeros(0)
+    if real.size != int(np.prod(dims)):
+        raise FormatError(f"MAT variable {name}: {real.size} values for dims {dims}")
+    a = real.astype(np.dtype(_MX[cls]).newbyteorder("=")).reshape(dims, order="F")
+    return name, (a != 0) if logical else a
+
+
+def read_mat(path):
+    """-> {name: ndarray} of the full numeric / logical variables of a level-5 MAT file."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    if len(buf) < 128:
+        raise FormatError(f"{path}: not a MAT file")
+    if buf[512:516] == b"\x89HDF" or b"MATLAB 7.3" in buf[:116]:
+        raise FormatError(f"{path}: MAT v7.3 (HDF5) files are not supported; save with -v7 (or -v6) instead")
+    end = {b"IM": "<", b"MI": ">"}.get(buf[126:128])
+    if end is None or not buf[:6] == b"MATLAB":
+        raise FormatError(f"{path}: not a level-5 MAT file")
+    out = {}
+
+    def visit(data):
+        for typ, payload in _elements(data, end):
+            if typ == MI_COMPRESSED:
+                visit(zlib.decompress(payload))
+            elif typ == MI_MATRIX:
+                name, a = _matrix(payload, end)
+                if a is not None:
+                    out[name] = a
+
+    visit(buf[128:])
+    return out

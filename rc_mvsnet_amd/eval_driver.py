@@ -106,10 +106,25 @@ def run_scans(model, args, device, rank, world):
             fusion.filter_depth(os.path.join(args.testpath, scan), folder, folder, os.path.join(args.outdir, scan + ".ply"),
                                 args.prob_thres, args.num_consistency, args.img_dist_thres, args.depth_thres,
                                 num_stage=nstage, device=str(device))
+            if args.dtu_gt:
+                score_scan(args, scan, device)
     if times:
         warm = times[1:] or times
         print(f"rank {rank}/{world}: {len(mine)} of {len(scans)} scans, {len(times)} reference views, "
               f"{1.0 / (sum(warm) / len(warm)):.1f} ref-views/s (model time), outputs under {args.outdir}")
+
+
+def score_scan(args, scan, device):
+    """--dtu-gt: DTU accuracy / completeness of the cloud --filter just wrote (rc_mvsnet_amd.dtu_eval), one JSON line per scan."""
+    import json
+    import re
+    from . import dtu_eval
+    m = re.fullmatch(r"scan(\d+)", scan)
+    if not m:
+        raise SystemExit(f"eval_driver: --dtu-gt scores DTU scans named scan<N>, not {scan!r}")
+    r = dtu_eval.evaluate_files(args.outdir, args.dtu_gt, int(m.group(1)), device=str(device))
+    print(json.dumps(r), flush=True)
+    return r
 
 
 def main(argv=None):
@@ -123,6 +138,8 @@ def main(argv=None):
     ap.add_argument("--max_w", type=int, default=1600)
     ap.add_argument("--io_threads", type=int, default=4, help="threads decoding input images ahead / writing outputs behind the GPU")
     ap.add_argument("--filter", action="store_true", help="fuse each scan's depth maps into <outdir>/<scan>.ply afterwards")
+    ap.add_argument("--dtu-gt", default=None, help="DTU MVS_Data folder: after --filter, score each fused cloud (accuracy / completeness, "
+                                                   "rc_mvsnet_amd.dtu_eval)")
     ap.add_argument("--prob_thres", type=float, default=0.8)
     ap.add_argument("--num_consistency", type=int, default=3)
     ap.add_argument("--img_dist_thres", type=float, default=0.5)
@@ -141,6 +158,8 @@ def main(argv=None):
     ap.add_argument("--procs-per-gpu", type=int, default=1, help="worker processes per GPU: items are independent, two processes per GPU overlap "
                                                                  "each other's latency-bound phases (rc_mvsnet_amd/sharding.py)")
     args = ap.parse_args(argv)
+    if args.dtu_gt and not args.filter:
+        raise SystemExit("eval_driver: --dtu-gt scores the clouds of --filter; give both")
     nproc = args.gpus * args.procs_per_gpu
     if nproc > 1 and not launched():
         raise SystemExit(launch_ranks("rc_mvsnet_amd.eval_driver", nproc, sys.argv[1:] if argv is None else argv, module=True))

@@ -313,3 +313,44 @@ def write_tanks_fusion_scan(scan, scan_folder, out_folder):
         os.makedirs(out_folder, exist_ok=True)
         shutil.rmtree(os.path.join(out_folder, sub), ignore_errors=True)
         shutil.move(os.path.join(scan_folder, sub), os.path.join(out_folder, sub))
+
+
+def dtu_eval_scan(n_stl=20000, n_data=24000, extent=120.0, res=4.0, seed=0, outlier_frac=0.02, cluster_frac=0.05, noise=0.3):
+    """A DTU-like scoring problem (rc_mvsnet_amd/dtu_eval.py): smooth height-field patches as the ground truth (stl, uniform
+    samples), the reconstruction (data) = samples of the same patches with Gaussian noise, dense clusters (spacing well below
+    0.2 mm) and far outliers; an ObsMask of Res-sized voxels around the stl points (dilated by one voxel), its BB and a ground
+    plane that leaves a slab of stl points below it.  -> dict data (n_data,3) fp32, stl (n_stl,3) fp32, obs_mask (s1,s2,s3)
+    bool indexed [x,y,z], bb (2,3) fp64, res, plane (4,) fp64."""
+    rng = np.random.default_rng(seed)
+    n_patch = 6
+
+    def patch_points(k, n):
+        p = rng.integers(0, n_patch, n)
+        u = rng.random(n) * 0.45 * extent
+        v = rng.random(n) * 0.45 * extent
+        ox, oy = (p % 3) * 0.32 * extent, (p // 3) * 0.5 * extent
+        x, y = ox + u, oy + v
+        z = 0.1 * extent * (1 + p % 2) + 3.0 * np.sin(0.05 * x + p) + 2.0 * np.cos(0.07 * y - p)
+        return np.stack([x, y, z], 1)
+
+    stl = patch_points(0, n_stl)
+    n_out = int(outlier_frac * n_data)
+    n_clu = int(cluster_frac * n_data)
+    surf = patch_points(1, n_data - n_out - n_clu) + rng.normal(0, noise, (n_data - n_out - n_clu, 3))
+    centres = patch_points(2, max(1, n_clu // 50))
+    clusters = centres[rng.integers(0, len(centres), n_clu)] + rng.normal(0, 0.05, (n_clu, 3))
+    lo, hi = stl.min(0), stl.max(0)
+    far = lo - 0.5 * extent + rng.random((n_out, 3)) * (hi - lo + extent)
+    data = np.concatenate([surf, clusters, far])[rng.permutation(n_data)]
+    bb = np.stack([lo - 10.0, hi + 10.0]).astype(np.float64)
+    size = np.floor((bb[1] - bb[0]) / res).astype(int) + 1
+    v = np.floor((stl - bb[0]) / res + 0.5).astype(int)
+    mask = np.zeros(size, dtype=bool)
+    mask[v[:, 0], v[:, 1], v[:, 2]] = True
+    grown = mask.copy()
+    for a in range(3):
+        for s in (-1, 1):
+            grown |= np.roll(mask, s, axis=a)
+    plane = np.array([0.0, 0.0, 1.0, -(lo[2] + 2.0)])
+    return {"data": data.astype(np.float32), "stl": stl.astype(np.float32), "obs_mask": grown, "bb": bb, "res": float(res),
+            "plane": plane}
