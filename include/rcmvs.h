@@ -570,6 +570,22 @@ int rcmvs_pc_select(const float* pts, const double* d, long long n, int mode, co
 /* stats[3] = {count, mean, variance (N - 1)} of x[0 .. *count) in fp64 (NaN for an empty set, variance 0 for one value);
  * part: RCMVS_PC_MOMENT_BLOCKS doubles of work. */
 int rcmvs_pc_moments(const double* x, const int* count, double* part, double* stats, void* stream);
+/* MeshSupSamp (matlab_eval/MeshSupSamp_web, the 'Surfaces' input): verts (nv,3) fp32, faces (m,3) int32 -> out (nv + samples, 3)
+ * fp32 = the vertices, then the samples of face 0, 1, ... each in MeshSupSamp's c1-major order, every sample computed in fp64
+ * (csrc/pointcloud_math.h) and rounded to fp32 once.  Three steps, the host reading totals in between:
+ * rows:  tri_rows (m) ints = non-empty rows of each face; totals[3] (uint64) is zeroed, then totals[0] = all rows, totals[1] =
+ *        faces with an index outside 0 .. nv-1 (those faces give nothing).  The caller refuses the mesh when totals[1] != 0 or
+ *        nv + totals[0] >= 2^31 (every non-empty row holds a point), before allocating anything row-sized.
+ * count: nrows = totals[0]; scan_work (ceil(max(m, nrows) / 2048) + 1) ints; tri_row_start (m + 1) and row_len (nrows) ints;
+ *        totals[2] = all samples.  The caller refuses nv + totals[2] >= 2^31 before allocating out.
+ * emit:  n_samples = totals[2]; row_start (nrows + 1) ints of work. */
+int rcmvs_pc_mesh_rows(const float* verts, long long nv, const int* faces, long long m, double dst, int* tri_rows,
+                       unsigned long long* totals, void* stream);
+int rcmvs_pc_mesh_count(const float* verts, long long nv, const int* faces, long long m, double dst, const int* tri_rows,
+                        long long nrows, int* scan_work, int* tri_row_start, int* row_len, unsigned long long* totals, void* stream);
+int rcmvs_pc_mesh_emit(const float* verts, long long nv, const int* faces, long long m, double dst, const int* tri_row_start,
+                       const int* row_len, long long nrows, long long n_samples, int* scan_work, int* row_start, float* out,
+                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,13 @@
 //             points still undecided ends the host's loop.
 //   select    DataInMask / StlAbovePlane and the outlier threshold, compacted in point order, then fp64 moments
 //             (two passes, fixed summation tree).
+//   mesh      MeshSupSamp (the 'Surfaces' input): one thread per face counts its non-empty rows, one thread per row its
+//             points (binary searches, pointcloud_math.h), int64 totals for the host's 2^31 check; the scans of both give the
+//             output slots, and one thread per output point finds its row and face by binary search (narrowed to the block's
+//             range) and writes the vertices, then the samples, through LDS as contiguous dwords.
 // gfx950 only; only plain atomics, __syncthreads, ballots and shuffles (tests/emu compiles this file too).
+#include <climits>
+
 #include "common.h"
 #include "pointcloud_math.h"
 
@@ -368,6 +374,122 @@ __global__ __launch_bounds__(64) void pc_moment_final_kernel(const double* __res
     }
 }
 
+
+// ---- mesh super-sampling (MeshSupSamp) ------------------------------------------------------------------------------
+constexpr int MS_BLOCK = 256;
+
+// face t's triangle; false when an index lies outside 0 .. nv-1
+__device__ inline bool ms_face(const float* __restrict__ verts, int nv, const int* __restrict__ faces, int t, double dst, pc::SubTri* tri) {
+    const int a = faces[(long long)t * 3 + 0], b = faces[(long long)t * 3 + 1], c = faces[(long long)t * 3 + 2];
+    if (a < 0 || a >= nv || b < 0 || b >= nv || c < 0 || c >= nv) return false;
+    pc::subtri_setup(verts + (long long)a * 3, verts + (long long)b * 3, verts + (long long)c * 3, dst, tri);
+    return true;
+}
+
+// *total += the block's sum of v (one atomic per block)
+__device__ inline void ms_block_add(unsigned long long v, unsigned long long* sh, unsigned long long* total) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = MS_BLOCK / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && sh[0]) atomicAdd(total, sh[0]);
+}
+
+// the last i in [lo, hi) with start[i] <= x (start non-decreasing, start[lo] <= x)
+__device__ inline int ms_locate(const int* __restrict__ start, int lo, int hi, int x) {
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (start[mid] <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// tri_rows[t] = non-empty rows of face t (saturated to INT_MAX); totals[0] += the rows (each capped at 2^31), totals[1] += bad faces
+__global__ __launch_bounds__(MS_BLOCK) void pc_mesh_rows_kernel(const float* __restrict__ verts, int nv, const int* __restrict__ faces, int m,
+                                                                double dst, int* __restrict__ tri_rows, unsigned long long* __restrict__ totals) {
+    __shared__ unsigned long long sh[MS_BLOCK];
+    const int t = blockIdx.x * MS_BLOCK + threadIdx.x;
+    long long rows = 0;
+    bool bad = false;
+    if (t < m) {
+        pc::SubTri tri;
+        if (ms_face(verts, nv, faces, t, dst, &tri)) rows = pc::subtri_rows(tri.n1, tri.n2);
+        else bad = true;
+        tri_rows[t] = (int)min(rows, (long long)INT_MAX);
+    }
+    const int nbad = __syncthreads_count(bad);
+    ms_block_add((unsigned long long)rows, sh, &totals[0]);
+    if (threadIdx.x == 0 && nbad) atomicAdd(&totals[1], (unsigned long long)nbad);
+}
+
+// row r (of face t = the last with tri_row_start[t] <= r, c1 = r - tri_row_start[t]): row_len[r] = its points; *total += them
+__global__ __launch_bounds__(MS_BLOCK) void pc_mesh_row_len_kernel(const float* __restrict__ verts, int nv, const int* __restrict__ faces, int m,
+                                                                   double dst, const int* __restrict__ tri_row_start, int nrows,
+                                                                   int* __restrict__ row_len, unsigned long long* __restrict__ total) {
+    __shared__ unsigned long long sh[MS_BLOCK];
+    __shared__ int range[2];
+    const int r0 = blockIdx.x * MS_BLOCK;
+    const int r = r0 + threadIdx.x;
+    if (threadIdx.x < 2) {
+        const int x = threadIdx.x == 0 ? r0 : (int)min((long long)r0 + MS_BLOCK, (long long)nrows) - 1;
+        range[threadIdx.x] = ms_locate(tri_row_start, 0, m, x);
+    }
+    __syncthreads();
+    long long len = 0;
+    if (r < nrows) {
+        const int t = ms_locate(tri_row_start, range[0], range[1] + 1, r);
+        pc::SubTri tri;
+        if (ms_face(verts, nv, faces, t, dst, &tri)) len = pc::subtri_row_len((double)(r - tri_row_start[t]), tri.n1, tri.n2);
+        row_len[r] = (int)min(len, (long long)INT_MAX);
+    }
+    ms_block_add((unsigned long long)len, sh, total);
+}
+
+// output point o < n_out: the vertex o, or sample s = o - nv of row r (the last with row_start[r] <= s, c2 = s - row_start[r])
+__global__ __launch_bounds__(MS_BLOCK) void pc_mesh_emit_kernel(const float* __restrict__ verts, int nv, const int* __restrict__ faces, int m,
+                                                                double dst, const int* __restrict__ tri_row_start, const int* __restrict__ row_start,
+                                                                int nrows, int n_out, float* __restrict__ out) {
+    __shared__ int range[4];                                     // the block's first / last row, then their faces
+    __shared__ float stage[3 * MS_BLOCK];
+    const int o0 = blockIdx.x * MS_BLOCK;
+    const int last = (int)min((long long)o0 + MS_BLOCK, (long long)n_out) - 1;
+    const int o = o0 + threadIdx.x;
+    if (threadIdx.x < 2 && last >= nv) {
+        const int s = threadIdx.x == 0 ? max(o0 - nv, 0) : last - nv;
+        const int r = ms_locate(row_start, 0, nrows, s);
+        range[threadIdx.x] = r;
+        range[2 + threadIdx.x] = ms_locate(tri_row_start, 0, m, r);
+    }
+    __syncthreads();
+    float p[3] = {0.0f, 0.0f, 0.0f};
+    if (o <= last) {
+        if (o < nv) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) p[k] = verts[(long long)o * 3 + k];
+        } else {
+            const int s = o - nv;
+            const int r = ms_locate(row_start, range[0], range[1] + 1, s);
+            const int t = ms_locate(tri_row_start, range[2], range[3] + 1, r);
+            pc::SubTri tri;
+            if (ms_face(verts, nv, faces, t, dst, &tri)) {
+                const double c1 = (double)(r - tri_row_start[t]), c2 = (double)(s - row_start[r]);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) p[k] = (float)pc::subtri_coord(tri, c1, c2, k);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) p[k] = NAN;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) stage[threadIdx.x * 3 + k] = p[k];
+    __syncthreads();
+    const int nf = (last - o0 + 1) * 3;
+    for (int i = threadIdx.x; i < nf; i += MS_BLOCK) out[(long long)o0 * 3 + i] = stage[i];
+}
+
 }  // namespace rcmvs
 
 using namespace rcmvs;
@@ -492,4 +614,49 @@ extern "C" int rcmvs_pc_moments(const double* x, const int* count, double* part,
         hipLaunchKernelGGL(pc_moment_final_kernel, dim3(1), dim3(64), 0, st, part, count, pass, stats);
     }
     return launch_status("pc_moments");
+}
+
+static int pc_mesh_args(const float* verts, long long nv, const int* faces, long long m, double dst, const char* who) {
+    RCMVS_REQUIRE(verts && faces, "%s: null pointer", who);
+    RCMVS_REQUIRE(nv > 0 && nv < (1ll << 31) && m > 0 && m < (1ll << 31), "%s: nv=%lld m=%lld (1 .. 2^31-1)", who, nv, m);
+    RCMVS_REQUIRE(dst > 0.0 && std::isfinite(dst), "%s: dst %g", who, dst);
+    return 0;
+}
+
+extern "C" int rcmvs_pc_mesh_rows(const float* verts, long long nv, const int* faces, long long m, double dst, int* tri_rows,
+                                  unsigned long long* totals, void* stream) {
+    if (int rc = pc_mesh_args(verts, nv, faces, m, dst, "pc_mesh_rows")) return rc;
+    RCMVS_REQUIRE(tri_rows && totals, "pc_mesh_rows: null pointer");
+    hipStream_t st = as_stream(stream);
+    if (hipMemsetAsync(totals, 0, 3 * sizeof(unsigned long long), st) != hipSuccess) return launch_status("pc_mesh_rows: memset");
+    hipLaunchKernelGGL(pc_mesh_rows_kernel, dim3((int)cdiv(m, MS_BLOCK)), dim3(MS_BLOCK), 0, st, verts, (int)nv, faces, (int)m, dst, tri_rows, totals);
+    return launch_status("pc_mesh_rows");
+}
+
+extern "C" int rcmvs_pc_mesh_count(const float* verts, long long nv, const int* faces, long long m, double dst, const int* tri_rows,
+                                   long long nrows, int* scan_work, int* tri_row_start, int* row_len, unsigned long long* totals,
+                                   void* stream) {
+    if (int rc = pc_mesh_args(verts, nv, faces, m, dst, "pc_mesh_count")) return rc;
+    RCMVS_REQUIRE(tri_rows && scan_work && tri_row_start && row_len && totals, "pc_mesh_count: null pointer");
+    RCMVS_REQUIRE(nrows > 0 && nv + nrows < (1ll << 31), "pc_mesh_count: %lld rows for %lld vertices (1 .. 2^31-1 points)", nrows, nv);
+    hipStream_t st = as_stream(stream);
+    pc_scan(tri_rows, (int)m, scan_work, tri_row_start, st);
+    hipLaunchKernelGGL(pc_mesh_row_len_kernel, dim3((int)cdiv(nrows, MS_BLOCK)), dim3(MS_BLOCK), 0, st, verts, (int)nv, faces, (int)m, dst,
+                       tri_row_start, (int)nrows, row_len, &totals[2]);
+    return launch_status("pc_mesh_count");
+}
+
+extern "C" int rcmvs_pc_mesh_emit(const float* verts, long long nv, const int* faces, long long m, double dst, const int* tri_row_start,
+                                  const int* row_len, long long nrows, long long n_samples, int* scan_work, int* row_start, float* out,
+                                  void* stream) {
+    if (int rc = pc_mesh_args(verts, nv, faces, m, dst, "pc_mesh_emit")) return rc;
+    RCMVS_REQUIRE(tri_row_start && row_len && scan_work && row_start && out, "pc_mesh_emit: null pointer");
+    RCMVS_REQUIRE(nrows > 0 && n_samples >= nrows && nv + n_samples < (1ll << 31),
+                  "pc_mesh_emit: %lld samples in %lld rows for %lld vertices (at most 2^31-1 points)", n_samples, nrows, nv);
+    hipStream_t st = as_stream(stream);
+    pc_scan(row_len, (int)nrows, scan_work, row_start, st);
+    const long long n_out = nv + n_samples;
+    hipLaunchKernelGGL(pc_mesh_emit_kernel, dim3((int)cdiv(n_out, MS_BLOCK)), dim3(MS_BLOCK), 0, st, verts, (int)nv, faces, (int)m, dst,
+                       tri_row_start, row_start, (int)nrows, (int)n_out, out);
+    return launch_status("pc_mesh_emit");
 }

@@ -14,8 +14,12 @@ GPU (csrc/pointcloud.hip):
 3. DataInMask / StlAbovePlane, the outlier threshold and ComputeStat_web_pt's statistics (fp64 sums, variance N - 1, the
    median of an even count = the mean of the two middle values, NaN for an empty set).
 
+Meshes (BaseEvalMain_web.m with representation 'Surfaces'): ``sample_mesh`` is MeshSupSamp's super-sampling (csrc/pointcloud.hip,
+samples computed in fp64 and rounded to fp32 once), ``evaluate_mesh`` scores that cloud as above, and ``error_colours`` /
+``write_error_clouds`` give BaseEval2Obj_web.m's coloured clouds as binary PLY (MATLAB writes text OBJ).
+
 CUDA tensors only; no CPU fallback.  ``python -m rc_mvsnet_amd.dtu_eval --plydir OUT --gtpath MVS_Data`` scores the clouds
-``eval_driver --filter`` wrote.
+``eval_driver --filter`` wrote; ``--surfaces --pattern ...`` scores meshes.
 """
 import argparse
 import ctypes
@@ -285,6 +289,98 @@ def evaluate_scan(data, stl, obs_mask, bb, res, plane, dst=0.2, outlier=20.0, se
     return out
 
 
+def sample_mesh(verts, faces, dst=0.2):
+    """MeshSupSamp (BaseEvalMain_web.m's 'Surfaces' input): verts (n,3) fp32 and faces (m,3) int (0-based) on the device ->
+    (n + samples, 3) fp32: the vertices, then the samples of face 0, 1, ... in MeshSupSamp's order.  Every sample is computed in
+    fp64 as MeshSupSamp.cpp's SubTri does and rounded to fp32 once (MATLAB keeps the double: at most half an fp32 ulp apart).
+    Raises RcmvsError for an index outside 0 .. n-1 and, before allocating the cloud, for 2^31 points or more."""
+    nv = _points(verts, "verts")
+    _chk(faces.contiguous(), "faces", faces.dtype)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.RcmvsError(f"faces: expected an (m,3) tensor, got {tuple(faces.shape)}")
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise _lib.RcmvsError(f"faces: integer indices expected, got {faces.dtype}")
+    if not (dst > 0 and math.isfinite(dst)):
+        raise _lib.RcmvsError(f"sample_mesh: dst {dst}")
+    m = faces.shape[0]
+    if m >= 1 << 31:
+        raise _lib.RcmvsError(f"sample_mesh: {m} faces (below 2^31)")
+    if m == 0:
+        return verts.clone()
+    if nv == 0:
+        raise _lib.RcmvsError("sample_mesh: faces without vertices")
+    if faces.dtype != torch.int32:
+        if int(faces.min()) < 0 or int(faces.max()) >= nv:
+            raise _lib.RcmvsError(f"sample_mesh: face indices outside 0 .. {nv - 1}")
+        faces = faces.to(torch.int32)
+    faces = faces.contiguous()
+    dev, lib, dst = verts.device, _lib.load(), float(dst)
+    args = (_chk(verts, "verts"), nv, _chk(faces, "faces", torch.int32), m, dst)
+    tri_rows = torch.empty(m, device=dev, dtype=torch.int32)
+    totals = torch.empty(3, device=dev, dtype=torch.int64)
+    _lib.check(lib.rcmvs_pc_mesh_rows(*args, _chk(tri_rows, "tri_rows", torch.int32), _chk(totals, "totals", torch.int64), _stream()),
+               "pc_mesh_rows")
+    rows, bad = totals[:2].tolist()
+    if bad:
+        raise _lib.RcmvsError(f"sample_mesh: {bad} faces index outside 0 .. {nv - 1}")
+    if nv + rows >= 1 << 31:
+        raise _lib.RcmvsError(f"sample_mesh: {nv} vertices + at least {rows} samples (dst {dst}): the scorer takes below 2^31 points")
+    if rows == 0:
+        return verts.clone()
+    scan_work = torch.empty(_cdiv(max(m, rows), SCAN_TILE) + 1, device=dev, dtype=torch.int32)
+    tri_row_start = torch.empty(m + 1, device=dev, dtype=torch.int32)
+    row_len = torch.empty(rows, device=dev, dtype=torch.int32)
+    _lib.check(lib.rcmvs_pc_mesh_count(*args, _chk(tri_rows, "tri_rows", torch.int32), rows, _chk(scan_work, "scan_work", torch.int32),
+                                       _chk(tri_row_start, "tri_row_start", torch.int32), _chk(row_len, "row_len", torch.int32),
+                                       _chk(totals, "totals", torch.int64), _stream()), "pc_mesh_count")
+    samples = int(totals[2])
+    if nv + samples >= 1 << 31:
+        raise _lib.RcmvsError(f"sample_mesh: {nv} vertices + {samples} samples (dst {dst}): the scorer takes below 2^31 points")
+    row_start = torch.empty(rows + 1, device=dev, dtype=torch.int32)
+    out = torch.empty((nv + samples, 3), device=dev, dtype=torch.float32)
+    _lib.check(lib.rcmvs_pc_mesh_emit(*args, _chk(tri_row_start, "tri_row_start", torch.int32), _chk(row_len, "row_len", torch.int32),
+                                      rows, samples, _chk(scan_work, "scan_work", torch.int32), _chk(row_start, "row_start", torch.int32),
+                                      _chk(out, "out"), _stream()), "pc_mesh_emit")
+    return out
+
+
+def evaluate_mesh(verts, faces, stl, obs_mask, bb, res, plane, dst=0.2, outlier=20.0, seed=0, order=None, per_point=False):
+    """BaseEvalMain_web.m with representation 'Surfaces': sample_mesh(verts, faces, dst), then evaluate_scan on that cloud
+    (order, if given, is a permutation of its points)."""
+    data = sample_mesh(verts, faces, dst)
+    return evaluate_scan(data, stl, obs_mask, bb, res, plane, dst=dst, outlier=outlier, seed=seed, order=order, per_point=per_point)
+
+
+ERROR_CAP = 10.0                                    # BaseEval2Obj_web.m's dist_tresshold (mm)
+
+
+def error_colours(d, flag):
+    """BaseEval2Obj_web.m's colours as (n,3) uint8 on d's device: alpha = min(d, 10) / 10; flag set: [1 0 0] alpha + [1 1 1]
+    (1 - alpha) (white to red), clear: [0 1 0] alpha + [0 0 1] (1 - alpha) (blue to green); stored as floor(255 C + 0.5)."""
+    a = torch.clamp(d.to(torch.float64), max=ERROR_CAP) / ERROR_CAP
+    b = 1.0 - a
+    f = flag.to(device=d.device, dtype=torch.bool)
+    zero = torch.zeros_like(a)
+    c = torch.where(f[:, None], torch.stack([a + b, b, b], 1), torch.stack([zero, a, b], 1))
+    return torch.floor(255.0 * c + 0.5).to(torch.uint8)
+
+
+def write_error_clouds(result, stl, out_dir, method, scan):
+    """BaseEval2Obj_web.m as two binary PLY files (MATLAB writes text OBJ): <method>2Stl_<scan>.ply (the reduced data coloured by
+    Ddata / DataInMask) and Stl2<method>_<scan>.ply (the stl points by Dstl / StlAbovePlane).  result: evaluate_scan(...,
+    per_point=True).  -> the two paths."""
+    from .fusion import ply_bytes
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for name, pts, d, flag in ((f"{method}2Stl_{scan}.ply", result["Qdata"], result["Ddata"], result["DataInMask"]),
+                               (f"Stl2{method}_{scan}.ply", stl, result["Dstl"], result["StlAbovePlane"])):
+        path = os.path.join(out_dir, name)
+        with open(path, "wb") as f:
+            f.write(ply_bytes(pts.cpu().numpy(), error_colours(d, flag).cpu().numpy()))
+        paths.append(path)
+    return paths
+
+
 def summarize(per_scan):
     """compute_mean.m over a list of evaluate_scan results: acc = mean(MeanData), comp = mean(MeanStl), overall = their mean."""
     acc = float(np.mean([s["MeanData"] for s in per_scan]))
@@ -293,20 +389,27 @@ def summarize(per_scan):
 
 
 # ---- files and command line -------------------------------------------------------------------------------------------
-def scan_paths(plydir, gtpath, scan):
-    """The four files of one scan: eval_driver's <plydir>/scan{N}.ply and the DTU ground truth of MVS_Data."""
-    return {"data": os.path.join(plydir, f"scan{scan}.ply"),
+def scan_paths(plydir, gtpath, scan, pattern="scan{scan}.ply"):
+    """The four files of one scan: <plydir>/<pattern formatted with scan=N> (default eval_driver's scan{N}.ply) and the DTU ground
+    truth of MVS_Data."""
+    return {"data": os.path.join(plydir, pattern.format(scan=scan)),
             "stl": os.path.join(gtpath, "Points", "stl", f"stl{scan:03d}_total.ply"),
             "mask": os.path.join(gtpath, "ObsMask", f"ObsMask{scan}_10.mat"),
             "plane": os.path.join(gtpath, "ObsMask", f"Plane{scan}.mat")}
 
 
-def evaluate_files(plydir, gtpath, scan, device="cuda:0", dst=0.2, outlier=20.0, seed=0):
-    """evaluate_scan on one scan's files -> the BaseStat dict (plus "scan")."""
-    from .dtu_io import read_mat, read_ply_xyz
-    p = scan_paths(plydir, gtpath, scan)
+def evaluate_files(plydir, gtpath, scan, device="cuda:0", dst=0.2, outlier=20.0, seed=0, pattern="scan{scan}.ply", surfaces=False,
+                   error_clouds=None, method="rcmvsnet"):
+    """evaluate_scan on one scan's files -> the BaseStat dict (plus "scan").  surfaces: the input is a triangle mesh, super-sampled
+    at dst first (evaluate_mesh).  error_clouds: a folder for BaseEval2Obj_web's two coloured clouds (write_error_clouds)."""
+    from .dtu_io import read_mat, read_ply_mesh, read_ply_xyz
+    p = scan_paths(plydir, gtpath, scan, pattern)
     dev = torch.device(device)
-    data = torch.from_numpy(read_ply_xyz(p["data"])).to(dev)
+    if surfaces:
+        verts, faces = read_ply_mesh(p["data"])
+        data = sample_mesh(torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev), dst)
+    else:
+        data = torch.from_numpy(read_ply_xyz(p["data"])).to(dev)
     stl = torch.from_numpy(read_ply_xyz(p["stl"])).to(dev)
     m = read_mat(p["mask"])
     for k in ("ObsMask", "BB", "Res"):
@@ -316,23 +419,37 @@ def evaluate_files(plydir, gtpath, scan, device="cuda:0", dst=0.2, outlier=20.0,
     if "P" not in pl:
         raise _lib.RcmvsError(f"{p['plane']}: no variable P")
     r = evaluate_scan(data, stl, torch.from_numpy(np.ascontiguousarray(m["ObsMask"]).astype(bool)), m["BB"],
-                      float(np.asarray(m["Res"]).ravel()[0]), np.asarray(pl["P"], dtype=np.float64).ravel(), dst=dst, outlier=outlier, seed=seed)
+                      float(np.asarray(m["Res"]).ravel()[0]), np.asarray(pl["P"], dtype=np.float64).ravel(), dst=dst, outlier=outlier, seed=seed,
+                      per_point=error_clouds is not None)
+    if error_clouds is not None:
+        write_error_clouds(r, stl, error_clouds, method, scan)
+        r = {k: r[k] for k in STAT_FIELDS}
     return dict(scan=scan, **r)
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="DTU accuracy / completeness (mm) of fused point clouds, on the GPU")
-    ap.add_argument("--plydir", required=True, help="folder of scan{N}.ply (what eval_driver --filter writes)")
+    ap = argparse.ArgumentParser(description="DTU accuracy / completeness (mm) of fused point clouds or meshes, on the GPU")
+    ap.add_argument("--plydir", required=True, help="folder of the inputs, named by --pattern (eval_driver --filter writes scan{N}.ply)")
     ap.add_argument("--gtpath", required=True, help="the DTU MVS_Data folder (Points/stl, ObsMask)")
     ap.add_argument("--scans", default=",".join(str(s) for s in USED_SETS), help="comma-separated scan numbers (default: GetUsedSets' 22)")
     ap.add_argument("--dst", type=float, default=0.2, help="reduction distance (mm)")
     ap.add_argument("--outlier", type=float, default=20.0, help="outlier threshold (mm)")
     ap.add_argument("--seed", type=int, default=0, help="seed of the reduction's visiting order")
     ap.add_argument("--gpus", type=int, default=1, help="GPUs of this node: scans are sharded one process per GPU, no collective")
+    ap.add_argument("--surfaces", action="store_true", help="the inputs are triangle meshes: super-sample them at --dst (MeshSupSamp) first")
+    ap.add_argument("--pattern", default="scan{scan}.ply", help="input file name, formatted with the scan number, e.g. "
+                    "'tola{scan:03d}_l3_surf_11_trim_8.ply' (default scan{scan}.ply)")
+    ap.add_argument("--error-clouds", default=None, metavar="DIR", help="also write BaseEval2Obj_web's coloured clouds "
+                    "<method>2Stl_<N>.ply and Stl2<method>_<N>.ply (binary PLY) into DIR")
+    ap.add_argument("--method", default="rcmvsnet", help="method name in the --error-clouds file names")
     ap.add_argument("--results-dir", default=None, help=argparse.SUPPRESS)      # ranks' results for the parent's summary
     args = ap.parse_args(argv)
     argv = sys.argv[1:] if argv is None else list(argv)
     scans = [int(s) for s in args.scans.split(",") if s.strip()]
+    try:
+        args.pattern.format(scan=scans[0] if scans else 1)
+    except (KeyError, IndexError, ValueError) as e:
+        ap.error(f"--pattern {args.pattern!r}: {e!r} (the one field is {{scan}})")
     from .sharding import launch_ranks, launched, rank_env, shard_items
     if args.gpus > 1 and not launched():
         with tempfile.TemporaryDirectory() as tmp:
@@ -355,7 +472,8 @@ def main(argv=None):
     _lib.load()
     results = []
     for scan in shard_items(scans, rank, world):
-        r = evaluate_files(args.plydir, args.gtpath, scan, device=device, dst=args.dst, outlier=args.outlier, seed=args.seed)
+        r = evaluate_files(args.plydir, args.gtpath, scan, device=device, dst=args.dst, outlier=args.outlier, seed=args.seed,
+                           pattern=args.pattern, surfaces=args.surfaces, error_clouds=args.error_clouds, method=args.method)
         results.append(r)
         print(json.dumps(r), flush=True)
     if args.results_dir:

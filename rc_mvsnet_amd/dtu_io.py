@@ -2,7 +2,8 @@
 
 ``read_ply_xyz``: ascii, binary_little_endian and binary_big_endian PLY, any scalar property types; returns the vertex element's
 x / y / z as (n,3) float32 and skips every other property and element (faces after the vertices included).  It reads what
-``fusion.ply_bytes`` writes and DTU's ``Points/stl/stl%03d_total.ply``.
+``fusion.ply_bytes`` writes and DTU's ``Points/stl/stl%03d_total.ply``.  ``read_ply_mesh``: the vertices and the triangles of
+a mesh PLY (the 'Surfaces' input of the scorer, what ``plyread.m`` gives MeshSupSamp).
 
 ``read_mat``: the MAT-file level 5 format (uncompressed and zlib-compressed variables), full numeric and logical arrays only,
 so that scipy is not a runtime dependency.  Arrays come back in MATLAB's index order (``a[i-1, j-1, k-1]`` is ``A(i,j,k)``).
@@ -107,6 +108,139 @@ def read_ply_xyz(path):
                 return np.stack([rec[k].astype(np.float32) for k in ("x", "y", "z")], axis=1)
             _skip_binary_element(f, count, props, end)
     raise FormatError(f"{path}: no vertex element")       # not reached
+
+
+_FACE_ELEMENTS = ("face", "Face", "poly", "Poly", "tri", "Tri")                        # the names plyread.m looks for
+_INDEX_PROPS = ("vertex_indices", "vertex_indexes", "vertex_index", "indices", "indexes")
+
+
+def _ascii_rows(tokens, pos, count, props, path, what):
+    """count rows of one ascii element from the token stream: -> (rows, each a list of per-property values, new pos)"""
+    rows = []
+    for _ in range(count):
+        row = []
+        for _, t in props:
+            if pos >= len(tokens):
+                raise FormatError(f"{path}: truncated {what} data")
+            if isinstance(t, tuple):
+                k = int(tokens[pos])
+                row.append(tokens[pos + 1:pos + 1 + k])
+                pos += 1 + k
+            else:
+                row.append(tokens[pos])
+                pos += 1
+        rows.append(row)
+    return rows, pos
+
+
+def _binary_faces(f, count, props, idx, end, path):
+    """-> (count, 3) int64 indices of a binary face element; a single list property with 3 indices per face is read at once"""
+    lists = [i for i, (_, t) in enumerate(props) if isinstance(t, tuple)]
+    if lists == [idx]:
+        _, cnt_t, idx_t = props[idx][1]
+        fields = [(f"p{i}", np.dtype(t).newbyteorder(end)) for i, (_, t) in enumerate(props) if i != idx]
+        fields.insert(idx, ("n", np.dtype(cnt_t).newbyteorder(end)))
+        fields.insert(idx + 1, ("i", np.dtype(idx_t).newbyteorder(end), (3,)))
+        dt = np.dtype(fields)
+        here = f.tell()
+        buf = f.read(dt.itemsize * count)
+        rec = np.frombuffer(buf[:len(buf) - len(buf) % dt.itemsize], dtype=dt)
+        bad = np.nonzero(rec["n"] != 3)[0]
+        if len(rec) == count and not len(bad):
+            return rec["i"].astype(np.int64)
+        # the first face that is not a triangle was read at its true offset: name it
+        k = int(bad[0]) if len(bad) else None
+        if k is not None:
+            raise FormatError(f"{path}: face {k} has {int(rec['n'][k])} vertices (only triangles are supported)")
+        f.seek(here)
+    out = np.empty((count, 3), dtype=np.int64)
+    for r in range(count):
+        for i, (_, t) in enumerate(props):
+            if isinstance(t, tuple):
+                cdt = np.dtype(t[1]).newbyteorder(end)
+                b = f.read(cdt.itemsize)
+                if len(b) != cdt.itemsize:
+                    raise FormatError(f"{path}: truncated face data")
+                k = int(np.frombuffer(b, dtype=cdt)[0])
+                idt = np.dtype(t[2]).newbyteorder(end)
+                b = f.read(k * idt.itemsize)
+                if len(b) != k * idt.itemsize:
+                    raise FormatError(f"{path}: truncated face data")
+                if i == idx:
+                    if k != 3:
+                        raise FormatError(f"{path}: face {r} has {k} vertices (only triangles are supported)")
+                    out[r] = np.frombuffer(b, dtype=idt)
+            else:
+                f.seek(np.dtype(t).itemsize, 1)
+    return out
+
+
+def read_ply_mesh(path):
+    """-> (verts (n,3) float32, faces (m,3) int32) of a triangle mesh PLY (ascii or binary, either byte order).  The faces are
+    the first element plyread.m would take (face, Face, poly, Poly, tri, Tri) with its index list (vertex_indices,
+    vertex_indexes, vertex_index, indices, indexes; any integer types); other properties are skipped.  No face element gives
+    (0,3) faces.  Refused with FormatError: non-triangle faces, indices outside 0 .. n-1, non-finite vertices."""
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f)
+        names = [e[0] for e in elements]
+        if "vertex" not in names:
+            raise FormatError(f"{path}: no vertex element")
+        face_name = next((k for k in _FACE_ELEMENTS if k in names), None)
+        vprops = elements[names.index("vertex")][2]
+        pnames = [p for p, _ in vprops]
+        for k in ("x", "y", "z"):
+            if k not in pnames:
+                raise FormatError(f"{path}: vertex has no property {k}")
+        if any(isinstance(t, tuple) for _, t in vprops):
+            raise FormatError(f"{path}: list properties in the vertex element are not supported")
+        idx = None
+        if face_name is not None:
+            fprops = elements[names.index(face_name)][2]
+            fnames = [p for p, _ in fprops]
+            idx = next((fnames.index(k) for k in _INDEX_PROPS if k in fnames), None)
+            if idx is None or not isinstance(fprops[idx][1], tuple):
+                raise FormatError(f"{path}: element {face_name} has no vertex index list")
+            if np.dtype(fprops[idx][1][2]).kind not in "iu" or np.dtype(fprops[idx][1][1]).kind not in "iu":
+                raise FormatError(f"{path}: face indices must be integers")
+        verts, faces = None, np.zeros((0, 3), dtype=np.int64)
+        if fmt == "ascii":
+            tokens = f.read().decode("ascii").split()
+            pos = 0
+            for name, count, props in elements:
+                rows, pos = _ascii_rows(tokens, pos, count, props, path, name)
+                if name == "vertex":
+                    cols = [pnames.index(k) for k in ("x", "y", "z")]
+                    verts = np.array([[float(r[c]) for c in cols] for r in rows], dtype=np.float64).astype(np.float32).reshape(count, 3)
+                elif name == face_name:
+                    bad = next((r for r, row in enumerate(rows) if len(row[idx]) != 3), None)
+                    if bad is not None:
+                        raise FormatError(f"{path}: face {bad} has {len(rows[bad][idx])} vertices (only triangles are supported)")
+                    faces = np.array([[int(v) for v in row[idx]] for row in rows], dtype=np.int64).reshape(count, 3)
+        else:
+            end = "<" if fmt == "binary_little_endian" else ">"
+            done = 0
+            for name, count, props in elements:
+                if name == "vertex":
+                    dt = np.dtype([(p, np.dtype(t).newbyteorder(end)) for p, t in props])
+                    buf = f.read(dt.itemsize * count)
+                    if len(buf) != dt.itemsize * count:
+                        raise FormatError(f"{path}: truncated vertex data")
+                    rec = np.frombuffer(buf, dtype=dt)
+                    verts = np.stack([rec[k].astype(np.float32) for k in ("x", "y", "z")], axis=1).reshape(count, 3)
+                    done += 1
+                elif name == face_name:
+                    faces = _binary_faces(f, count, props, idx, end, path)
+                    done += 1
+                else:
+                    _skip_binary_element(f, count, props, end)
+                if done == (1 if face_name is None else 2):
+                    break
+    if not np.isfinite(verts).all():
+        raise FormatError(f"{path}: non-finite vertex coordinates")
+    n = len(verts)
+    if len(faces) and (faces.min() < 0 or faces.max() >= n):
+        raise FormatError(f"{path}: face indices outside 0 .. {n - 1}")
+    return verts, faces.astype(np.int32).reshape(-1, 3)
 
 
 # ---- MAT v5 --------------------------------------------------------------------------------------------------------------

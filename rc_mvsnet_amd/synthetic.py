@@ -342,6 +342,13 @@ def dtu_eval_scan(n_stl=20000, n_data=24000, extent=120.0, res=4.0, seed=0, outl
     lo, hi = stl.min(0), stl.max(0)
     far = lo - 0.5 * extent + rng.random((n_out, 3)) * (hi - lo + extent)
     data = np.concatenate([surf, clusters, far])[rng.permutation(n_data)]
+    return dict(data=data.astype(np.float32), **_dtu_truth(stl, res))
+
+
+def _dtu_truth(stl, res):
+    """stl (n,3) fp64 -> the scan's stl (fp32), an ObsMask of Res-sized voxels around the stl points (dilated by one voxel), its BB
+    (the stl box widened by 10) and a ground plane 2 above the lowest stl point."""
+    lo, hi = stl.min(0), stl.max(0)
     bb = np.stack([lo - 10.0, hi + 10.0]).astype(np.float64)
     size = np.floor((bb[1] - bb[0]) / res).astype(int) + 1
     v = np.floor((stl - bb[0]) / res + 0.5).astype(int)
@@ -352,5 +359,31 @@ def dtu_eval_scan(n_stl=20000, n_data=24000, extent=120.0, res=4.0, seed=0, outl
         for s in (-1, 1):
             grown |= np.roll(mask, s, axis=a)
     plane = np.array([0.0, 0.0, 1.0, -(lo[2] + 2.0)])
-    return {"data": data.astype(np.float32), "stl": stl.astype(np.float32), "obs_mask": grown, "bb": bb, "res": float(res),
-            "plane": plane}
+    return {"stl": stl.astype(np.float32), "obs_mask": grown, "bb": bb, "res": float(res), "plane": plane}
+
+
+def _height(x, y):
+    return 3.0 * np.sin(0.05 * x) + 2.0 * np.cos(0.07 * y) + 0.5 * np.sin(0.9 * x + 0.4 * y)
+
+
+def dtu_eval_mesh(nx=200, ny=150, edge=0.4, n_stl=20000, res=4.0, seed=0, offset=0.15, jitter=0.25):
+    """A DTU-like mesh scoring problem (dtu_eval.evaluate_mesh): the reconstruction is a triangulated height field over an
+    nx x ny vertex grid of spacing ``edge`` (two triangles per cell, vertices jittered in x / y by up to ``jitter`` * edge and
+    raised by a smooth error of amplitude ``offset``); the ground truth (stl) is n_stl uniform samples of the exact surface, with
+    ObsMask and BB as in dtu_eval_scan and a ground plane above the lowest fifth of the surface.  -> dict verts (nx*ny,3) fp32, faces (2(nx-1)(ny-1),3) int32, stl, obs_mask, bb,
+    res, plane."""
+    rng = np.random.default_rng(seed)
+    gx, gy = np.meshgrid(np.arange(nx) * edge, np.arange(ny) * edge, indexing="xy")
+    x = gx + (rng.random(gx.shape) - 0.5) * 2 * jitter * edge
+    y = gy + (rng.random(gy.shape) - 0.5) * 2 * jitter * edge
+    z = _height(x, y) + offset * np.sin(0.3 * x) * np.cos(0.2 * y)
+    verts = np.stack([x.ravel(), y.ravel(), z.ravel()], 1)
+    i = (np.arange(ny - 1)[:, None] * nx + np.arange(nx - 1)[None, :]).ravel()
+    faces = np.concatenate([np.stack([i, i + 1, i + nx], 1), np.stack([i + 1, i + nx + 1, i + nx], 1)]).astype(np.int32)
+    su = rng.random(n_stl) * (nx - 1) * edge
+    sv = rng.random(n_stl) * (ny - 1) * edge
+    stl = np.stack([su, sv, _height(su, sv)], 1)
+    truth = _dtu_truth(stl, res)
+    zlo, zhi = stl[:, 2].min(), stl[:, 2].max()
+    truth["plane"] = np.array([0.0, 0.0, 1.0, -(zlo + 0.2 * (zhi - zlo))])     # the lowest fifth of the surface lies below it
+    return dict(verts=verts.astype(np.float32), faces=faces, **truth)
