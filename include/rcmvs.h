@@ -587,6 +587,22 @@ int rcmvs_pc_mesh_emit(const float* verts, long long nv, const int* faces, long 
                        const int* row_len, long long nrows, long long n_samples, int* scan_work, int* row_start, float* out,
                        void* stream);
 
+/* ---- training loader: image preparation (csrc/train_aug.hip; additive, RCMVS_VERSION stays 106) ----
+ * src (V,H,W,3) uint8: the decoded views of one item.  params: per view 8 32-bit words = float factor[4] (brightness,
+ * contrast, saturation >= 0 and finite; hue in [-0.5, 0.5]) then int order[4] (a permutation of 0..3 = brightness, contrast,
+ * saturation, hue: the order ColorJitter applies them in).  params_host is read for validation, params_dev (the same
+ * bytes on the device) by the kernels.  H W < 2^29, 1 <= V <= 65535.
+ * stats: sums (V,8) uint64 is zeroed and receives per view {sum x (3 channels), sum x^2 (3), sum of L when contrast's turn
+ *        comes, unused} -- exact integers.
+ * apply: lut_seg (3,256) and lut_aug (V,3,256) fp32 = the value of each byte after ToTensor (+ gamma, clamp) + Normalize;
+ *        imgs, center_imgs, imgs_aug (V,3,H,W) fp32; u8_out NULL or (V,H,W,3) uint8 = ColorJitter's bytes (equal to
+ *        Pillow's).  Reads the sums of a stats call on the same src and params, enqueued before it on the same stream. */
+int rcmvs_train_image_stats(const unsigned char* src, int V, int H, int W, const void* params_host, const void* params_dev,
+                            unsigned long long* sums, void* stream);
+int rcmvs_train_image_apply(const unsigned char* src, int V, int H, int W, const void* params_host, const void* params_dev,
+                            const unsigned long long* sums, const float* lut_seg, const float* lut_aug, float* imgs,
+                            float* center_imgs, float* imgs_aug, unsigned char* u8_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

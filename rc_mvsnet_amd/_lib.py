@@ -120,6 +120,9 @@ SIGNATURES = {
     "rcmvs_pc_mesh_rows": [_p, _ll, _p, _ll, _d, _p, _p, _p],
     "rcmvs_pc_mesh_count": [_p, _ll, _p, _ll, _d, _p, _ll, _p, _p, _p, _p, _p],
     "rcmvs_pc_mesh_emit": [_p, _ll, _p, _ll, _d, _p, _p, _ll, _ll, _p, _p, _p, _p],
+    # training loader: image preparation (additive entry points of version 106)
+    "rcmvs_train_image_stats": [_p, _i, _i, _i, _p, _p, _p, _p],
+    "rcmvs_train_image_apply": [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
 }
 _RESTYPES = {"rcmvs_last_error_string": ctypes.c_char_p, "rcmvs_nerf_weight_floats": _ll, "rcmvs_nerf_workspace_floats": _ll, "rcmvs_nerf_train_workspace_floats": _ll, "rcmvs_nerf_bwd_workspace_floats": _ll,
              "rcmvs_packed_weight_floats": _ll, "rcmvs_fpn_folded_mfma_floats": _ll, "rcmvs_conv2d_pair_weight_floats": _ll, "rcmvs_conv2d_stem_weight_floats": _ll, "rcmvs_conv2d_tile_weight_floats": _ll}

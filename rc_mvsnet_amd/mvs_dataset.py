@@ -11,6 +11,10 @@ host parses the text files and decodes the JPEG; ``/255``, the ``cv2.resize`` of
 ``ToTensor`` and ``Normalize`` are one kernel per image (``rcmvs_prepare_image``) on the uploaded bytes -- that work costs the
 reference's single loader worker ~10x the network's time per item.  ``imgs`` is therefore a CUDA tensor; everything else is
 numpy like the reference's.  No CPU fallback: ``device`` must be a GPU.
+
+``DTUTrainDataset`` is the training counterpart (datasets/dtu_train.py, ``--dataset dtu_train``): the host decodes every PNG
+once and parses cameras / depth maps; ``imgs``, ``center_imgs`` and the colour-augmented ``imgs_aug`` of all views come from
+two launches of csrc/train_aug.hip (``prepare_train_images``).  DESIGN.md section 4, "Training loader".
 """
 import ctypes
 import os
@@ -20,6 +24,7 @@ import torch
 from PIL import Image
 
 from . import _lib, scan_io
+from .data_io import read_pfm
 from .ops import _chk, _stream
 
 MEAN = (0.485, 0.456, 0.406)      # transforms.Normalize of datasets/dtu_test.py:78-81
@@ -249,3 +254,240 @@ class TanksDataset(torch.utils.data.Dataset):
 
     def __getitem__(self, idx):
         return self.to_device(self.load_host(idx))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# training loader (datasets/dtu_train.py)
+# ---------------------------------------------------------------------------------------------------------------------
+JITTER_RANGES = ((0.0, 2.0), (0.0, 2.0), (0.5, 1.5), (-0.5, 0.5))   # ColorJitter(brightness=1, contrast=1, saturation=0.5, hue=0.5)
+GAMMA_RANGE = (0.5, 2.0)                                            # RandomGamma(min_gamma=0.5, max_gamma=2.0, clip_image=True)
+TRAIN_HW = (512, 640)                                               # prepare_img's crop (dtu_train.py:164-178)
+TRAIN_RAW_HW = (1200, 1600)                                         # the depth / mask maps of Depths_raw
+
+
+def tone_table(gamma=None, mean=MEAN, std=STD):
+    """(3,256) fp32: what ToTensor [+ RandomGamma(gamma, clip_image=True)] + Normalize make of each byte value, computed with
+    the torch CPU ops the reference applies to the whole image (datasets/utils.py:52-57), so the kernel's values are torch's."""
+    t = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255)
+    if gamma is not None:
+        t = torch.pow(t, float(gamma))
+        t.clamp_(0.0, 1.0)
+    t = t.view(1, 256).repeat(3, 1)
+    return t.sub_(torch.as_tensor(mean, dtype=torch.float32).view(3, 1)).div_(torch.as_tensor(std, dtype=torch.float32).view(3, 1))
+
+
+def draw_aug(generator, nviews):
+    """Per-view augmentation parameters from ``generator``: ``order`` (V,4) int32 permutations of (brightness, contrast,
+    saturation, hue), ``factors`` (V,4) fp32 in JITTER_RANGES, ``gamma`` (V,) fp64 in GAMMA_RANGE."""
+    order = np.stack([torch.randperm(4, generator=generator).numpy() for _ in range(nviews)]).astype(np.int32)
+    u = torch.rand((nviews, 5), generator=generator, dtype=torch.float64).numpy()
+    lo = np.array([r[0] for r in JITTER_RANGES] + [GAMMA_RANGE[0]])
+    hi = np.array([r[1] for r in JITTER_RANGES] + [GAMMA_RANGE[1]])
+    v = lo + u * (hi - lo)
+    factors = np.clip(v[:, :4].astype(np.float32), lo[:4].astype(np.float32), hi[:4].astype(np.float32))   # fp32 rounding stays inside
+    return {"order": order, "factors": factors, "gamma": v[:, 4].copy()}
+
+
+def prepare_train_images(raw_u8, aug, device, return_u8=False):
+    """Decoded views (V,H,W,3) uint8 numpy + ``aug`` (see draw_aug) -> {"imgs", "center_imgs", "imgs_aug"}: (V,3,H,W) fp32
+    tensors on ``device`` (rcmvs_train_image_stats + rcmvs_train_image_apply); ``return_u8`` adds "jitter_u8" (V,H,W,3), the
+    bytes ColorJitter produced (equal to Pillow's)."""
+    raw_u8 = np.asarray(raw_u8)
+    if raw_u8.dtype != np.uint8 or raw_u8.ndim != 4 or raw_u8.shape[3] != 3:
+        raise _lib.RcmvsError(f"prepare_train_images: expected (V,H,W,3) uint8 views, got {raw_u8.dtype} {raw_u8.shape}")
+    V, H, W = raw_u8.shape[:3]
+    order = np.ascontiguousarray(aug["order"], dtype=np.int32)
+    factors = np.ascontiguousarray(aug["factors"], dtype=np.float32)
+    gamma = np.asarray(aug["gamma"], dtype=np.float64)
+    if order.shape != (V, 4) or factors.shape != (V, 4) or gamma.shape != (V,):
+        raise _lib.RcmvsError(f"prepare_train_images: parameters of {V} views expected, got order {order.shape}, factors {factors.shape}, "
+                              f"gamma {gamma.shape}")
+    if not (np.isfinite(gamma).all() and (gamma > 0).all()):
+        raise _lib.RcmvsError(f"prepare_train_images: gamma must be finite and > 0, got {gamma}")
+    params = np.ascontiguousarray(np.concatenate([factors.view(np.int32), order], axis=1))            # (V,8) words: ta::ViewParams
+    lib = _lib.load()
+    src = torch.from_numpy(np.ascontiguousarray(raw_u8)).to(device, non_blocking=True)
+    params_dev = torch.from_numpy(params).to(device, non_blocking=True)
+    lut_seg = tone_table().to(device, non_blocking=True)
+    lut_aug = torch.stack([tone_table(g) for g in gamma]).to(device, non_blocking=True)
+    sums = torch.empty((V, 8), device=device, dtype=torch.int64)
+    out = {k: torch.empty((V, 3, H, W), device=device, dtype=torch.float32) for k in ("imgs", "center_imgs", "imgs_aug")}
+    u8 = torch.empty((V, H, W, 3), device=device, dtype=torch.uint8) if return_u8 else None
+    host = ctypes.c_void_p(params.ctypes.data)
+    _lib.check(lib.rcmvs_train_image_stats(_chk(src, "src", torch.uint8), V, H, W, host, _chk(params_dev, "params", torch.int32),
+                                           _chk(sums, "sums", torch.int64), _stream()), "train_image_stats")
+    _lib.check(lib.rcmvs_train_image_apply(_chk(src, "src", torch.uint8), V, H, W, host, _chk(params_dev, "params", torch.int32),
+                                           _chk(sums, "sums", torch.int64), _chk(lut_seg, "lut_seg"), _chk(lut_aug, "lut_aug"),
+                                           _chk(out["imgs"], "imgs"), _chk(out["center_imgs"], "center_imgs"), _chk(out["imgs_aug"], "imgs_aug"),
+                                           ctypes.c_void_p(0) if u8 is None else _chk(u8, "u8_out", torch.uint8), _stream()),
+               "train_image_apply")
+    if return_u8:
+        out["jitter_u8"] = u8
+    out["sums"] = sums
+    return out
+
+
+def _half_crop(raw, what):
+    """prepare_img / read_depth_all (dtu_train.py:164-178,195-205): cv2.resize(INTER_NEAREST) to exactly half the size picks
+    source index 2 * dst, then the centre crop to 512 x 640 -- strided slicing.  Only the raw size the reference's hard-coded
+    crop ([44:556, 80:720] of the halved map) is written for is accepted."""
+    if raw.shape != TRAIN_RAW_HW:
+        raise _lib.RcmvsError(f"{what}: raw size {raw.shape} is not {TRAIN_RAW_HW}, the only one the reference's crop handles")
+    return np.ascontiguousarray(raw[88:1112:2, 160:1440:2])
+
+
+def _pyramid(full):
+    return {"stage1": np.ascontiguousarray(full[::4, ::4]), "stage2": np.ascontiguousarray(full[::2, ::2]), "stage3": full}
+
+
+class DTUTrainDataset(torch.utils.data.Dataset):
+    """datasets/dtu_train.py ``MVSDataset`` (the training set of Yao Yao's preprocessed DTU):
+
+        <datapath>/Cameras/pair.txt, Cameras/train/<view:08d>_cam.txt
+        <datapath>/Rectified/<scan>_train/rect_<view+1:03d>_<light>_r5000.png            (512 x 640)
+        <datapath>/Depths_raw/<scan>/depth_map_<view:04d>.pfm, depth_visual_<view:04d>.png  (1200 x 1600)
+
+    One item per scan x viewpoint x light (7).  Same keys and shapes as the reference's item; ``imgs``, ``imgs_aug`` and
+    ``center_imgs`` are CUDA tensors, the rest numpy.  The augmentation's random draws come from a generator seeded from
+    (seed, epoch, idx) -- ``set_epoch`` -- and travel with the host half as ``host["aug"]``."""
+
+    def __init__(self, datapath, listfile, mode, nviews, ndepths=192, interval_scale=1.06, random_view=False, device="cuda:0", seed=0):
+        super().__init__()
+        if mode not in ("train", "val"):
+            raise ValueError(f"DTUTrainDataset: mode {mode!r} is not 'train' or 'val' (evaluation folders: MVSDataset)")
+        self.datapath, self.listfile, self.mode, self.nviews, self.ndepths = datapath, listfile, mode, nviews, ndepths
+        self.interval_scale, self.random_view, self.device, self.seed, self.epoch = interval_scale, random_view, torch.device(device), seed, 0
+        self.metas = self.build_list()
+        self.build_proj_mats()
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def build_list(self):
+        with open(self.listfile) as f:
+            scans = [line.rstrip() for line in f.readlines()]
+        pairs = []
+        with open(os.path.join(self.datapath, "Cameras/pair.txt")) as f:
+            for _ in range(int(f.readline())):
+                ref = int(f.readline().rstrip())
+                pairs.append((ref, [int(x) for x in f.readline().rstrip().split()[1::2]]))
+        metas = [(scan, light, ref, srcs) for scan in scans for ref, srcs in pairs for light in range(7)]
+        self.id_list = np.unique(np.concatenate([[ref] + srcs for ref, srcs in pairs]).astype(np.int64)) if scans else np.zeros(0, np.int64)
+        self.remap = np.zeros(int(self.id_list.max()) + 1 if len(self.id_list) else 0, dtype=int)
+        self.remap[self.id_list] = np.arange(len(self.id_list))
+        return metas
+
+    def read_cam_file(self, filename):
+        """-> intrinsics, extrinsics (fp32), depth_min, depth_interval * interval_scale, [depth_min, depth_max] (dtu_train.py:113-125)"""
+        lines = scan_io._cam_lines(filename)
+        tail = lines[11].split()
+        depth_min, depth_interval = float(tail[0]), float(tail[1]) * self.interval_scale
+        return (scan_io._matrix(lines[7:10], 3, 3), scan_io._matrix(lines[1:5], 4, 4), depth_min, depth_interval,
+                [depth_min, depth_min + depth_interval * self.ndepths])
+
+    def build_proj_mats(self):
+        """Per camera of the pair file: the full-resolution intrinsics, the 4x4 projection at quarter resolution (float64, from
+        an fp32 product, as dtu_train.py:31-54 forms it), near / far, world-to-camera and its inverse."""
+        self.proj_mats, self.near_fars, intr, w2c, c2w = [], [], [], [], []
+        for vid in self.id_list:
+            K, E, _, _, near_far = self.read_cam_file(os.path.join(self.datapath, f"Cameras/train/{vid:08d}_cam.txt"))
+            K[:2] *= 4
+            intr.append(K.copy())
+            K[:2] = K[:2] / 4
+            P = np.eye(4)
+            P[:3, :4] = K @ E[:3, :4]
+            self.proj_mats.append(P)
+            self.near_fars.append(near_far)
+            w2c.append(E)
+            c2w.append(np.linalg.inv(E))
+        self.intrinsics_nerf, self.world2cams, self.cam2worlds = np.stack(intr), np.stack(w2c), np.stack(c2w)
+
+    def __len__(self):
+        return len(self.metas)
+
+    def generator(self, idx):
+        """The item's own random stream: a function of (seed, epoch, idx) only, not of the thread or order that loads it."""
+        mix = ((int(self.seed) * 0x9E3779B1 + int(self.epoch)) * 0x85EBCA6B + int(idx)) & 0x7FFFFFFFFFFFFFFF
+        return torch.Generator().manual_seed(mix)
+
+    def load_host(self, idx):
+        """Everything of item ``idx`` that needs no GPU: PNG / PFM decoding (every file once), camera parsing, the depth and mask
+        pyramids, the renderer's matrices, and the augmentation draws.  Thread-safe (``prefetch`` runs it on worker threads)."""
+        scan, light_idx, ref_view, src_views = self.metas[idx]
+        g = self.generator(idx)
+        if self.random_view:
+            pick = torch.randperm(len(src_views), generator=g)[:self.nviews - 1]
+            view_ids = [ref_view] + [src_views[int(i)] for i in pick]
+        else:
+            view_ids = [ref_view] + src_views[:self.nviews - 1]
+        raws, proj_matrices, depths_h, proj_mats, affine, affine_inv, intr, w2cs, c2ws, near_fars = [], [], [], [], [], [], [], [], [], []
+        for i, vid in enumerate(view_ids):
+            img_name = os.path.join(self.datapath, "Rectified/{}_train/rect_{:0>3}_{}_r5000.png".format(scan, vid + 1, light_idx))
+            mask_name = os.path.join(self.datapath, "Depths_raw/{}/depth_visual_{:0>4}.png".format(scan, vid))
+            depth_name = os.path.join(self.datapath, "Depths_raw/{}/depth_map_{:0>4}.pfm".format(scan, vid))
+            raw = np.array(Image.open(img_name).convert("RGB"), dtype=np.uint8)
+            if raws and raw.shape != raws[0].shape:
+                raise _lib.RcmvsError(f"view {vid} of {scan}: size {raw.shape[:2]} differs from the reference view's {raws[0].shape[:2]}")
+            raws.append(raw)
+            k = self.remap[vid]
+            P = self.proj_mats[k]
+            intr.append(self.intrinsics_nerf[k])
+            w2cs.append(self.world2cams[k])
+            c2ws.append(self.cam2worlds[k])
+            near_fars.append(self.near_fars[k])
+            affine.append(P)
+            affine_inv.append(np.linalg.inv(P))
+            if i == 0:
+                ref_inv = np.linalg.inv(P)
+                proj_mats.append(np.eye(4))
+            else:
+                proj_mats.append(P @ ref_inv)
+            depth_full = None
+            if os.path.exists(depth_name):
+                depth_full = _half_crop(read_pfm(depth_name)[0], depth_name)
+                depths_h.append(depth_full)
+            else:
+                depths_h.append(np.zeros((1, 1)))                   # dtu_train.py:303-308
+            K, E, depth_min, depth_interval, _ = self.read_cam_file(os.path.join(self.datapath, "Cameras/train/{:0>8}_cam.txt".format(vid)))
+            p = np.zeros((2, 4, 4), dtype=np.float32)
+            p[0, :4, :4] = E
+            p[1, :3, :3] = K
+            proj_matrices.append(p)
+            if i == 0:
+                if depth_full is None:
+                    raise _lib.RcmvsError(f"{depth_name}: the reference view's depth map is missing")
+                visual = np.array(Image.open(mask_name), dtype=np.float32)
+                mask = _pyramid(_half_crop((visual > 10).astype(np.float32), mask_name))
+                depth = _pyramid(depth_full)
+                depth_values = np.arange(depth_min, depth_interval * self.ndepths + depth_min, depth_interval, dtype=np.float32)
+        view_ids_all = [ref_view] + list(src_views)
+        return {"raw": np.stack(raws), "aug": draw_aug(g, len(view_ids)), "proj": np.stack(proj_matrices), "depth": depth, "mask": mask,
+                "depth_values": depth_values, "depths_h": np.stack(depths_h).astype(np.float32), "w2cs": np.stack(w2cs).astype(np.float32),
+                "c2ws": np.stack(c2ws).astype(np.float32), "near_fars": np.stack(near_fars).astype(np.float32),
+                "proj_mats": np.stack(proj_mats)[:, :3].astype(np.float32), "intrinsics": np.stack(intr).astype(np.float32),
+                "view_ids": np.array(view_ids), "light_id": np.array(light_idx), "affine_mat": np.stack(affine),
+                "affine_mat_inv": np.stack(affine_inv), "scan": scan, "c2ws_all": self.cam2worlds[self.remap[view_ids_all]].astype(np.float32)}
+
+    def to_device(self, host):
+        """The device half: two launches for all views' three image tensors, then the three-stage projection matrices."""
+        item = {k: v for k, v in host.items() if k not in ("raw", "aug", "proj")}
+        out = prepare_train_images(host["raw"], host["aug"], self.device)
+        item.update(imgs=out["imgs"], imgs_aug=out["imgs_aug"], center_imgs=out["center_imgs"])
+        proj = host["proj"]
+        stages = {"stage1": proj}
+        for key, mul in (("stage2", 2), ("stage3", 4)):
+            q = proj.copy()
+            q[:, 1, :2, :] = proj[:, 1, :2, :] * mul
+            stages[key] = q
+        item["proj_matrices"] = stages
+        return item
+
+    def __getitem__(self, idx):
+        return self.to_device(self.load_host(idx))
+
+    def render_batch(self, item):
+        """The dict train_step hands to Rendering_Consistency_Net (train_rcmvsnet.py:279-285): batch dimension added, on the device."""
+        dev = item["imgs"].device
+        batch = {k: torch.from_numpy(np.ascontiguousarray(item[k]))[None].to(dev) for k in ("w2cs", "c2ws", "intrinsics", "near_fars", "depths_h", "proj_mats")}
+        batch["imgs"] = item["imgs"][None]
+        return batch

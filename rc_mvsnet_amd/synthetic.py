@@ -387,3 +387,70 @@ def dtu_eval_mesh(nx=200, ny=150, edge=0.4, n_stl=20000, res=4.0, seed=0, offset
     zlo, zhi = stl[:, 2].min(), stl[:, 2].max()
     truth["plane"] = np.array([0.0, 0.0, 1.0, -(zlo + 0.2 * (zhi - zlo))])     # the lowest fifth of the surface lies below it
     return dict(verts=verts.astype(np.float32), faces=faces, **truth)
+
+
+# ----------------------------------------------------------------------------------------
+# a DTU training folder (datasets/dtu_train.py layout) for the training loader
+# ----------------------------------------------------------------------------------------
+def write_dtu_train_folder(folder, scans, n_views, seed, hw=(512, 640), raw_hw=(1200, 1600)):
+    """Write a small folder in the layout of Yao Yao's preprocessed DTU training set and return the path of its list file:
+
+        Cameras/pair.txt, Cameras/train/<view:08d>_cam.txt        quarter-resolution intrinsics of ``cameras(n_views, *hw)``
+        Rectified/<scan>_train/rect_<view+1:03d>_<light>_r5000.png  7 lights per view, ``hw`` RGB
+        Depths_raw/<scan>/depth_map_<view:04d>.pfm                  ``raw_hw`` depth of the smooth surface of ``fusion_scan``
+        Depths_raw/<scan>/depth_visual_<view:04d>.png               ``raw_hw`` 8-bit visibility (values around the loader's > 10 test)
+
+    Image pixel (y, x) is raw pixel (88 + 2 y, 160 + 2 x) for the default sizes, the relation the loader's half-size + centre crop
+    assumes.  Every view lists all the others as sources."""
+    import os
+    from PIL import Image
+    from .data_io import save_pfm
+    H, W = hw
+    RH, RW = raw_hw
+    Kq, Es = cameras(n_views, H, W)
+    Kf = Kq.copy()
+    Kf[:2] *= 4.0
+    os.makedirs(os.path.join(folder, "Cameras", "train"), exist_ok=True)
+    with open(os.path.join(folder, "Cameras", "pair.txt"), "w") as f:
+        f.write("%d\n" % n_views)
+        for v in range(n_views):
+            srcs = [(v + k) % n_views for k in range(1, n_views)]
+            f.write("%d\n%d %s\n" % (v, len(srcs), " ".join("%d %.3f" % (s, 100.0 - i) for i, s in enumerate(srcs))))
+    for v in range(n_views):
+        with open(os.path.join(folder, "Cameras", "train", "{:0>8}_cam.txt".format(v)), "w") as f:
+            f.write("extrinsic\n")
+            for row in Es[v].astype(np.float32):
+                f.write(" ".join(repr(float(x)) for x in row) + "\n")
+            f.write("\nintrinsic\n")
+            for row in Kq.astype(np.float32):
+                f.write(" ".join(repr(float(x)) for x in row) + "\n")
+            f.write("\n425.0 2.5\n")
+    # raw pixel -> ray of the full-resolution camera (x_img = (x_raw - ox) / 2)
+    oy, ox = (RH // 2 - H) // 2 * 2, (RW // 2 - W) // 2 * 2
+    ys, xs = np.meshgrid((np.arange(RH, dtype=np.float64) - oy) / 2.0, (np.arange(RW, dtype=np.float64) - ox) / 2.0, indexing="ij")
+    rays = np.linalg.inv(Kf) @ np.stack([xs.ravel(), ys.ravel(), np.ones(RH * RW)])
+    yy, xx = np.meshgrid(np.linspace(-1.0, 1.0, RH), np.linspace(-1.0, 1.0, RW), indexing="ij")
+    for si, scan in enumerate(scans):
+        rng = np.random.default_rng(seed + 1000 * si)
+        os.makedirs(os.path.join(folder, "Rectified", scan + "_train"), exist_ok=True)
+        os.makedirs(os.path.join(folder, "Depths_raw", scan), exist_ok=True)
+        for v in range(n_views):
+            Ei = np.linalg.inv(Es[v])
+            d = np.full(RH * RW, 650.0 + 5.0 * si)
+            for _ in range(4):                                    # fixed-point ray / surface intersection, as fusion_scan
+                Pw = Ei[:3, :3] @ (rays * d) + Ei[:3, 3:4]
+                d = d + (_surface(Pw[0], Pw[1]) + 5.0 * si - Pw[2])
+            save_pfm(os.path.join(folder, "Depths_raw", scan, "depth_map_{:0>4}.pfm".format(v)), d.reshape(RH, RW).astype(np.float32))
+            r2 = (xx / 0.9) ** 2 + (yy / 0.8) ** 2
+            visual = np.where(r2 < 1.0, 255, np.where(r2 < 1.1, 11, np.where(r2 < 1.2, 10, 0))).astype(np.uint8)
+            Image.fromarray(visual).save(os.path.join(folder, "Depths_raw", scan, "depth_visual_{:0>4}.png".format(v)), compress_level=1)
+            base = images(1, 1, H, W, seed + 100 * si + v)[0, 0].numpy().transpose(1, 2, 0)          # smooth, roughly unit range
+            base = base + 0.1 * rng.standard_normal((H, W, 3))
+            for light in range(7):
+                img = np.clip(128.0 + (40.0 + 8.0 * light) * base, 0.0, 255.0).astype(np.uint8)
+                Image.fromarray(img).save(os.path.join(folder, "Rectified", scan + "_train", "rect_{:0>3}_{}_r5000.png".format(v + 1, light)),
+                                          compress_level=1)
+    lst = os.path.join(folder, "train_list.txt")
+    with open(lst, "w") as f:
+        f.write("".join(s + "\n" for s in scans))
+    return lst

@@ -56,11 +56,15 @@ def synthetic_sample(device, H=512, W=640, V=4, seed=0):
 DLOSSW = (0.5, 1.0, 2.0)      # --dlossw default, train_rcmvsnet.py:61
 
 
-def train_step(model, model_nerf, opt, imgs, proj, depth_values, batch, w_aug=0.01, cascade_fn=None, render_fn=None, grad_sync=None):
+def train_step(model, model_nerf, opt, imgs, proj, depth_values, batch, w_aug=0.01, cascade_fn=None, render_fn=None, grad_sync=None,
+               imgs_aug=None, loss_imgs=None):
     """One iteration with the reference's losses (train_rcmvsnet.py:279-312,330-376,397-446); returns a dict of scalar losses
     (python floats).  cascade_fn(model, imgs, proj, depth_values) / render_fn(model_nerf, volume_feature, pseudo_depth, batch)
     default to the modules' own forward.  grad_sync: a parallel.GradSync over both models (data-parallel training: the
-    gradients live in its flat buffer and are averaged over the ranks with one message before the optimizer step)."""
+    gradients live in its flat buffer and are averaged over the ranks with one message before the optimizer step).
+    imgs_aug / loss_imgs (B,V,3,H,W): what a training loader supplies (mvs_dataset.DTUTrainDataset) -- the colour-augmented
+    images forward #2 reads (sample["imgs_aug"], :410-415) and the per-image centred images the photometric loss reads
+    (sample["center_imgs"], :345).  None (synthetic inputs) uses ``imgs`` in their place."""
     from . import losses
     cascade_fn = cascade_fn or (lambda m, *a: m(*a))
     render_fn = render_fn or (lambda m, *a: m(*a))
@@ -72,10 +76,11 @@ def train_step(model, model_nerf, opt, imgs, proj, depth_values, batch, w_aug=0.
         opt.zero_grad(set_to_none=True)
     dlossw = list(DLOSSW)
     outputs, volume_feature = cascade_fn(model, imgs, proj, depth_values)          # forward #1 (:342)
-    loss_base, _ = losses.UnsupLossMultiStage()(outputs, imgs, proj, dlossw=dlossw)  # (:345)
+    loss_base, _ = losses.UnsupLossMultiStage()(outputs, imgs if loss_imgs is None else loss_imgs, proj, dlossw=dlossw)  # (:345)
     pseudo_depth = outputs["depth"].detach()
-    ref_img, filter_mask = losses.random_image_mask(imgs[:, 0], (imgs.shape[3] // 3, imgs.shape[4] // 3))   # (:412)
-    imgs_aug = torch.cat((ref_img.unsqueeze(1), imgs[:, 1:]), dim=1)
+    aug_src = imgs if imgs_aug is None else imgs_aug
+    ref_img, filter_mask = losses.random_image_mask(aug_src[:, 0], (imgs.shape[3] // 3, imgs.shape[4] // 3))   # (:412)
+    imgs_aug = torch.cat((ref_img.unsqueeze(1), aug_src[:, 1:]), dim=1)
     outputs_aug, _ = cascade_fn(model, imgs_aug, proj, depth_values)               # forward #2 (:415)
     loss_aug, _ = losses.AugLossMultiStage()(outputs_aug, pseudo_depth, None, filter_mask, dlossw=dlossw)
     loss_aug = loss_aug * w_aug                                                    # (:420-424)
