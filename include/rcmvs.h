@@ -603,6 +603,43 @@ int rcmvs_train_image_apply(const unsigned char* src, int V, int H, int W, const
                             const unsigned long long* sums, const float* lut_seg, const float* lut_aug, float* imgs,
                             float* center_imgs, float* imgs_aug, unsigned char* u8_out, void* stream);
 
+/* ---- validation: ground-truth depth metrics of one item (csrc/depth_metrics.hip; additive, RCMVS_VERSION stays 106) ----
+ * Replaces the scalar outputs of test_sample_depth (train_rcmvsnet.py:449-499): cas_mvsnet_loss (models/modules.py:527-546),
+ * AbsDepthError_metrics and Thres_metrics (utils.py:139-159), and its two masked images.  est / gt / mask of stage s: n_s
+ * floats each (batch 1).  With m = mask > 0.5, d = est - gt (one fp32 subtraction), e = |d|:
+ *   sl1_s = sum over m of (e < 1 ? 0.5 d^2 : e - 0.5), N_s = count(m); for stage 3 also sum e, count(e > T) for T = 2, 4, 8
+ *   (strict) and sum e / count of e in [0,2], [2,4], [4,8] (both ends inclusive: e = 2 is in two bands).
+ * Row `slot` of table (rows, RCMVS_DM_RECORD) doubles receives
+ *   [LOSS] sum_s w_s sl1_s / N_s   [DEPTH_LOSS] sl1_3 / N_3   [ABS_DEPTH_ERROR] sum e / N_3
+ *   [THRES_ERROR + k] count(e > T_k) / N_3   [THRES_ACCU + k] 1 - that   [THRES_ABSERROR + k] band mean (0 for an empty band)
+ *   [RAW ..] sl1_1..3, sum e, the three band sums, N_1..3, count(e > T_k), the three band counts (integers, exact); then zeros.
+ * An empty mask gives NaN (0 / 0) except in the band means; a NaN estimate fails every comparison and makes the sums NaN.
+ * dlossw_host: HOST array of 3 doubles or NULL (= 1, 1, 1).  masked_depth / errormap: NULL or n3 floats = est3 * mask3 and
+ * |est3 - gt3| * mask3.  workspace: rcmvs_depth_metrics_workspace_bytes(n1, n2, n3) bytes, 128-byte aligned, ZERO-FILLED ONCE by
+ * the caller; every call that completes leaves it ready for the next call on the same stream (after a failed or lost launch
+ * the ticket may be left part-drawn: zero-fill it again).  Sums are fp64 and added in a fixed order: two
+ * calls give identical bits.  No host synchronisation.  _timed: ev_start / ev_stop = hipEvent_t (or NULL) that receive the
+ * kernel's own start / stop timestamps. */
+#define RCMVS_DM_RECORD 32
+#define RCMVS_DM_LOSS 0
+#define RCMVS_DM_DEPTH_LOSS 1
+#define RCMVS_DM_ABS_DEPTH_ERROR 2
+#define RCMVS_DM_THRES_ERROR 3
+#define RCMVS_DM_THRES_ACCU 6
+#define RCMVS_DM_THRES_ABSERROR 9
+#define RCMVS_DM_RAW 12
+long long rcmvs_depth_metrics_workspace_bytes(long long n1, long long n2, long long n3);
+int rcmvs_depth_metrics(const float* est1, const float* gt1, const float* mask1, long long n1,
+                        const float* est2, const float* gt2, const float* mask2, long long n2,
+                        const float* est3, const float* gt3, const float* mask3, long long n3,
+                        const double* dlossw_host, double* table, int slot, float* masked_depth, float* errormap,
+                        void* workspace, void* stream);
+int rcmvs_depth_metrics_timed(const float* est1, const float* gt1, const float* mask1, long long n1,
+                              const float* est2, const float* gt2, const float* mask2, long long n2,
+                              const float* est3, const float* gt3, const float* mask3, long long n3,
+                              const double* dlossw_host, double* table, int slot, float* masked_depth, float* errormap,
+                              void* workspace, void* ev_start, void* ev_stop, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

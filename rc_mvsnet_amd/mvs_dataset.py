@@ -15,6 +15,10 @@ numpy like the reference's.  No CPU fallback: ``device`` must be a GPU.
 ``DTUTrainDataset`` is the training counterpart (datasets/dtu_train.py, ``--dataset dtu_train``): the host decodes every PNG
 once and parses cameras / depth maps; ``imgs``, ``center_imgs`` and the colour-augmented ``imgs_aug`` of all views come from
 two launches of csrc/train_aug.hip (``prepare_train_images``).  DESIGN.md section 4, "Training loader".
+
+``DTUValDataset`` is the validation loader over the same folders (datasets/dtu_yao.py in mode "test", what the reference's
+training script validates on): 5 views, images only divided by 255, the ground-truth depth and mask pyramids of the reference
+view.  ``validation.validate`` consumes it.  DESIGN.md section 4, "Validation".
 """
 import ctypes
 import os
@@ -491,3 +495,119 @@ class DTUTrainDataset(torch.utils.data.Dataset):
         batch = {k: torch.from_numpy(np.ascontiguousarray(item[k]))[None].to(dev) for k in ("w2cs", "c2ws", "intrinsics", "near_fars", "depths_h", "proj_mats")}
         batch["imgs"] = item["imgs"][None]
         return batch
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# validation loader (datasets/dtu_yao.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_STAGES = ("stage1", "stage2", "stage3")
+
+
+def _staging(array, device):
+    """numpy -> host tensor an upload starts from: page-locked for a GPU, so that ``.to(device, non_blocking=True)`` is
+    enqueued behind the running kernels instead of making the host wait for them (what a pageable copy does)."""
+    t = torch.from_numpy(np.ascontiguousarray(array))
+    return t.pin_memory() if device.type == "cuda" else t
+
+
+class DTUValDataset(torch.utils.data.Dataset):
+    """datasets/dtu_yao.py ``MVSDataset`` as train_rcmvsnet.py:518-519 builds it (mode "test", 5 views): the folder layout of
+    ``DTUTrainDataset``, one item per scan x viewpoint x light, views ``[ref] + src[:nviews-1]``, no augmentation and no
+    ImageNet normalisation.  Item = the reference's: ``imgs`` (V,3,H,W) = bytes / 255 in fp32 (a CUDA tensor, one
+    rcmvs_prepare_image launch per view on the uploaded bytes), ``proj_matrices`` {stage1..3: (V,2,4,4)}, ``depth`` / ``mask``
+    {stage1..3} of the reference view's Depths_raw files, ``depth_values``; all numpy but ``imgs``.  ``depth_dev`` / ``mask_dev``
+    are the same pyramids as (1,h,w) tensors on the device, ``proj_dev`` / ``depth_values_dev`` the batched (1,...) device copies
+    of the matrices and depth values: everything the forward and ``validation.depth_metrics`` read, uploaded with the item."""
+
+    def __init__(self, datapath, listfile, mode="test", nviews=5, ndepths=192, interval_scale=1.06, device="cuda:0"):
+        super().__init__()
+        if mode not in ("train", "val", "test"):
+            raise ValueError(f"DTUValDataset: mode {mode!r} is not 'train', 'val' or 'test'")
+        self.datapath, self.listfile, self.mode, self.nviews, self.ndepths = datapath, listfile, mode, nviews, ndepths
+        self.interval_scale, self.device = interval_scale, torch.device(device)
+        self.metas = self.build_list()
+
+    def build_list(self):
+        with open(self.listfile) as f:
+            scans = [line.rstrip() for line in f.readlines()]
+        pairs = []
+        with open(os.path.join(self.datapath, "Cameras/pair.txt")) as f:
+            for _ in range(int(f.readline())):
+                ref = int(f.readline().rstrip())
+                pairs.append((ref, [int(x) for x in f.readline().rstrip().split()[1::2]]))
+        return [(scan, light, ref, srcs) for scan in scans for ref, srcs in pairs for light in range(7)]
+
+    def __len__(self):
+        return len(self.metas)
+
+    def read_cam_file(self, filename):
+        """-> intrinsics, extrinsics (fp32), depth_min, depth_interval * interval_scale (dtu_yao.py:53-64)"""
+        lines = scan_io._cam_lines(filename)
+        tail = lines[11].split()
+        return scan_io._matrix(lines[7:10], 3, 3), scan_io._matrix(lines[1:5], 4, 4), float(tail[0]), float(tail[1]) * self.interval_scale
+
+    def load_host(self, idx):
+        """Everything of item ``idx`` that needs no GPU: PNG / PFM decoding, camera parsing, the depth and mask pyramids.
+        Thread-safe (``prefetch`` runs it on worker threads)."""
+        scan, light_idx, ref_view, src_views = self.metas[idx]
+        view_ids = [ref_view] + src_views[:self.nviews - 1]
+        raws, projs = [], []
+        for i, vid in enumerate(view_ids):
+            img_name = os.path.join(self.datapath, "Rectified/{}_train/rect_{:0>3}_{}_r5000.png".format(scan, vid + 1, light_idx))
+            raw = np.array(Image.open(img_name), dtype=np.uint8)
+            if raw.ndim != 3 or raw.shape[2] != 3:
+                raise _lib.RcmvsError(f"{img_name}: expected an RGB image, got shape {raw.shape}")
+            if raws and raw.shape != raws[0].shape:
+                raise _lib.RcmvsError(f"view {vid} of {scan}: size {raw.shape[:2]} differs from the reference view's {raws[0].shape[:2]}")
+            raws.append(raw)
+            K, E, depth_min, depth_interval = self.read_cam_file(os.path.join(self.datapath, "Cameras/train/{:0>8}_cam.txt".format(vid)))
+            p = np.zeros((2, 4, 4), dtype=np.float32)
+            p[0, :4, :4] = E
+            p[1, :3, :3] = K
+            projs.append(p)
+            if i == 0:
+                mask_name = os.path.join(self.datapath, "Depths_raw/{}/depth_visual_{:0>4}.png".format(scan, vid))
+                depth_name = os.path.join(self.datapath, "Depths_raw/{}/depth_map_{:0>4}.pfm".format(scan, vid))
+                visual = np.array(Image.open(mask_name), dtype=np.float32)
+                mask = _pyramid(_half_crop((visual > 10).astype(np.float32), mask_name))
+                depth = _pyramid(_half_crop(np.array(read_pfm(depth_name)[0], dtype=np.float32), depth_name))
+                depth_values = np.arange(depth_min, depth_interval * self.ndepths + depth_min, depth_interval, dtype=np.float32)
+        proj = np.stack(projs)
+        stages = {"stage1": proj}
+        for key, mul in (("stage2", 2), ("stage3", 4)):
+            q = proj.copy()
+            q[:, 1, :2, :] = proj[:, 1, :2, :] * mul
+            stages[key] = q
+        # one staging buffer for the bytes and one for every fp32 array the GPU reads: two uploads per item
+        small = np.concatenate([depth[k].ravel() for k in _STAGES] + [mask[k].ravel() for k in _STAGES] +
+                               [stages[k].ravel() for k in _STAGES] + [depth_values])
+        return {"raw": _staging(np.stack(raws), self.device), "f32": _staging(small, self.device), "proj_matrices": stages, "depth": depth,
+                "mask": mask, "depth_values": depth_values, "scan": scan, "view_ids": np.array(view_ids), "light_id": np.array(light_idx)}
+
+    def to_device(self, host):
+        """The device half: two uploads, one rcmvs_prepare_image launch per view (equal sizes, mean 0, std 1: float(b) / 255.0f),
+        then views of the fp32 upload."""
+        item = {k: v for k, v in host.items() if k not in ("raw", "f32")}
+        src = host["raw"].to(self.device, non_blocking=True)
+        V, H, W = src.shape[:3]
+        imgs = torch.empty((V, 3, H, W), device=self.device, dtype=torch.float32)
+        zero, one = (ctypes.c_float * 3)(0.0, 0.0, 0.0), (ctypes.c_float * 3)(1.0, 1.0, 1.0)
+        lib = _lib.load()
+        for v in range(V):
+            _lib.check(lib.rcmvs_prepare_image(_chk(src[v], "src", torch.uint8), _chk(imgs[v], "imgs"), H, W, H, W,
+                                               ctypes.cast(zero, ctypes.c_void_p), ctypes.cast(one, ctypes.c_void_p), _stream()), "prepare_image")
+        item["imgs"] = imgs
+        f32 = host["f32"].to(self.device, non_blocking=True)
+        at = 0
+        for key, shapes in (("depth_dev", [(1,) + host["depth"][k].shape for k in _STAGES]), ("mask_dev", [(1,) + host["mask"][k].shape for k in _STAGES]),
+                            ("proj_dev", [(1,) + host["proj_matrices"][k].shape for k in _STAGES])):
+            item[key] = {}
+            for k, shape in zip(_STAGES, shapes):
+                n = int(np.prod(shape))
+                item[key][k] = f32[at:at + n].view(shape)
+                at += n
+        item["depth_values_dev"] = f32[at:].view(1, -1)
+        return item
+
+    def __getitem__(self, idx):
+        return self.to_device(self.load_host(idx))
