@@ -640,6 +640,20 @@ int rcmvs_depth_metrics_timed(const float* est1, const float* gt1, const float* 
                               const double* dlossw_host, double* table, int slot, float* masked_depth, float* errormap,
                               void* workspace, void* ev_start, void* ev_stop, void* stream);
 
+/* ---- depth colour map (csrc/depth_colormap.hip; additive, RCMVS_VERSION stays 106) ----
+ * write_depth_img_2 of eval_rcmvsnet_tanks.py:141-154 up to the PNG encoder: vmin = min(depth), vmax = numpy's default (linear)
+ * percentile of the H * W values -- EXACT, a radix select over the fp32 bits, the virtual index (n - 1) * (percentile / 100) formed
+ * in fp32 as numpy does for an fp32 map -- then x = (d - vmin) / (vmax - vmin) in matplotlib's precision (the difference rounded
+ * to fp32, the division in fp64 rounded to fp32; csrc/depth_colormap_math.h), index trunc(256 x) into lut (256 x 3
+ * bytes, DEVICE; x == 1 is entry 255, above it entry 255, vmin == vmax gives entry 0 everywhere), rgb (H, W, 3) bytes.
+ * A map with a NaN has vmin = vmax = NaN and every pixel (0, 0, 0), as the reference writes it.  stats: 4 floats on the device =
+ * vmin, vmax, 1 if the map holds a NaN else 0, 0.  workspace: rcmvs_depth_colormap_workspace_bytes() bytes, 16-byte aligned, any
+ * contents (cleared by every call); calls that share one must be on one stream.  Four launches and a memset on `stream`, no host
+ * synchronisation; two calls give identical bytes.  H, W >= 1, H * W < 2^31, 0 <= percentile <= 100. */
+long long rcmvs_depth_colormap_workspace_bytes(void);
+int rcmvs_depth_colormap(const float* depth, int H, int W, double percentile, const unsigned char* lut, unsigned char* rgb,
+                         float* stats, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

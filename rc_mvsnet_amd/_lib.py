@@ -127,10 +127,13 @@ SIGNATURES = {
     "rcmvs_depth_metrics_workspace_bytes": [_ll, _ll, _ll],
     "rcmvs_depth_metrics": [_p, _p, _p, _ll, _p, _p, _p, _ll, _p, _p, _p, _ll, _p, _p, _i, _p, _p, _p, _p],
     "rcmvs_depth_metrics_timed": [_p, _p, _p, _ll, _p, _p, _p, _ll, _p, _p, _p, _ll, _p, _p, _i, _p, _p, _p, _p, _p, _p],
+    # depth colour map of the Tanks-and-Temples evaluation (additive entry points of version 106)
+    "rcmvs_depth_colormap_workspace_bytes": [],
+    "rcmvs_depth_colormap": [_p, _i, _i, _d, _p, _p, _p, _p, _p],
 }
 _RESTYPES = {"rcmvs_last_error_string": ctypes.c_char_p, "rcmvs_nerf_weight_floats": _ll, "rcmvs_nerf_workspace_floats": _ll, "rcmvs_nerf_train_workspace_floats": _ll, "rcmvs_nerf_bwd_workspace_floats": _ll,
              "rcmvs_packed_weight_floats": _ll, "rcmvs_fpn_folded_mfma_floats": _ll, "rcmvs_conv2d_pair_weight_floats": _ll, "rcmvs_conv2d_stem_weight_floats": _ll, "rcmvs_conv2d_tile_weight_floats": _ll,
-             "rcmvs_depth_metrics_workspace_bytes": _ll}
+             "rcmvs_depth_metrics_workspace_bytes": _ll, "rcmvs_depth_colormap_workspace_bytes": _ll}
 
 _lib = None
 

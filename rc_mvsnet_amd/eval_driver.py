@@ -8,8 +8,17 @@ are written next to the depth maps as the reference does (eval_rcmvsnet_dtu.py:2
 (``rc_mvsnet_amd.fusion.filter_depth``, the reference's step 2) on this rank's scans.  With real data the shard unit is the scan,
 so that a rank owns every depth map its fusion needs.
 
+``--dataset tanks`` is the reference's Tanks-and-Temples workflow (``save_depth`` + ``__main__`` of eval_rcmvsnet_tanks.py:158-202,385-503)
+in one command: ``mvs_dataset.TanksDataset`` items through the model, ``depth_est/<view>.pfm``, ``confidence/<view>.pfm`` and the
+colour-mapped ``depth_est/<view>.pfm.png`` (``rc_mvsnet_amd.depth_vis``: coloured on the device, encoded by the writer threads), then
+``fusion.filter_depth_tanks`` with the scene's settings (``fusion.TANKS_FILTER``) into ``<plydir>/<scene>.ply``.  The depth and
+confidence maps are handed to the fusion step on the device (``--resident-gb``), not read back from the files just written.
+The shard unit is the scene.
+
     python -m rc_mvsnet_amd.eval_driver --outdir out --scans 4 --views 3 --height 512 --width 640
     python -m rc_mvsnet_amd.eval_driver --outdir out --testpath /data/dtu_test --testlist lists/dtu/test.txt --loadckpt model.ckpt --filter
+    python -m rc_mvsnet_amd.eval_driver --dataset tanks --testpath /data/TankandTemples --split intermediate --outdir tanks_exp \
+        --plydir tanks_submission --loadckpt model.ckpt [--scenes Family,Horse] [--ndepths 64,32,8]
     python -m rc_mvsnet_amd.eval_driver --gpus 8 --procs-per-gpu 2 --outdir out ...          (starts its own 16 ranks, two per GPU)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m rc_mvsnet_amd.eval_driver --outdir out ...
 """
@@ -99,6 +108,10 @@ def run_scans(model, args, device, rank, world):
                     path = os.path.join(args.outdir, name.format(kind, ".pfm"))
                     os.makedirs(os.path.dirname(path), exist_ok=True)
                     writer.submit(save_pfm, path, t.float().cpu().numpy())
+                if args.depth_png:
+                    from . import depth_vis
+                    writer.submit(depth_vis.save_png, os.path.join(args.outdir, name.format("depth_est", ".pfm")) + ".png",
+                                  depth_vis.depth_colormap(out["depth"][0].float().contiguous())[0])
                 cam = item["proj_matrices"]["stage{}".format(nstage)][0]
                 writer.submit(save_reference_view, args.outdir, name, cam, item["imgs"][0].cpu())
         if args.filter:
@@ -112,6 +125,85 @@ def run_scans(model, args, device, rank, world):
         warm = times[1:] or times
         print(f"rank {rank}/{world}: {len(mine)} of {len(scans)} scans, {len(times)} reference views, "
               f"{1.0 / (sum(warm) / len(warm)):.1f} ref-views/s (model time), outputs under {args.outdir}")
+
+
+def tanks_scenes(args):
+    """The scenes this run covers, every argument error of ``--dataset tanks`` as one line, before the network is built."""
+    from .fusion import TANKS_FILTER
+    if not args.testpath:
+        raise SystemExit("eval_driver: --dataset tanks needs --testpath <TankandTemples folder>")
+    if args.split not in TANKS_FILTER:
+        raise SystemExit(f"eval_driver: --split {args.split} is not one of {', '.join(TANKS_FILTER)}")
+    known = TANKS_FILTER[args.split]
+    scenes = [s for s in args.scenes.split(",") if s] if args.scenes else list(known)
+    for s in scenes:
+        if s not in known:
+            raise SystemExit(f"eval_driver: {s!r} is not a scene of the {args.split} split ({', '.join(known)})")
+        pair = os.path.join(args.testpath, args.split, s, "pair.txt")
+        if not os.path.exists(pair):
+            raise SystemExit(f"eval_driver: {pair} is missing (a scene folder holds pair.txt, cams_1/ and images/)")
+    if args.max_h < 32 or args.max_w < 32 or args.max_h % 32 or args.max_w % 32:
+        raise SystemExit(f"eval_driver: --max_h {args.max_h} x --max_w {args.max_w}: the network's depth maps have that size only for multiples of 32 "
+                         "(the fusion step needs them at exactly --max_h x --max_w)")
+    if args.num_view < 2:
+        raise SystemExit(f"eval_driver: --num_view {args.num_view}: a reference view and at least one source view")
+    return scenes
+
+
+def run_tanks(model, args, device, rank, world):
+    """--dataset tanks: this rank's scenes through the loader, the model, the writers and the fusion step."""
+    from . import depth_vis, fusion
+    from .mvs_dataset import AsyncWriter, TanksDataset, prefetch
+    scenes = tanks_scenes(args)
+    mine = shard_items(scenes, rank, world)
+    img_wh = (args.max_w, args.max_h)
+    times, views_done = [], 0
+    for scene in mine:
+        ply = os.path.join(args.plydir, scene + ".ply")
+        if os.path.exists(ply):
+            print("{} exists. skipped.".format(ply))
+            continue
+        ds = TanksDataset(args.testpath, args.split, args.num_view, img_wh, args.numdepth, device=device, scans=[scene])
+        need = 2 * len(ds) * args.max_h * args.max_w * 4
+        resident = need <= args.resident_gb * 2 ** 30
+        if not resident:
+            print(f"eval_driver: {scene}: {len(ds)} views need {need / 2 ** 30:.1f} GB on the device, above --resident-gb {args.resident_gb:g}: "
+                  "the fusion step reads the PFM files back")
+        depth_maps, conf_maps = ({}, {}) if resident else (None, None)
+        with torch.no_grad(), AsyncWriter(args.io_threads) as writer:
+            for k, item in enumerate(prefetch(ds, workers=args.io_threads, depth=2 * args.io_threads)):
+                imgs = item["imgs"].unsqueeze(0)
+                proj = {s: torch.from_numpy(v).unsqueeze(0).to(device) for s, v in item["proj_matrices"].items()}
+                dv = torch.from_numpy(item["depth_values"]).unsqueeze(0).to(device)
+                t0 = time.perf_counter()
+                out = model(imgs, proj, dv)
+                if device.type == "cuda":
+                    torch.cuda.synchronize(device)
+                times.append(time.perf_counter() - t0)
+                depth, conf = out["depth"][0].float().contiguous(), out["photometric_confidence"][0].float().contiguous()
+                if tuple(depth.shape) != (args.max_h, args.max_w):
+                    raise SystemExit(f"eval_driver: the network's depth map is {tuple(depth.shape)}, not --max_h x --max_w = {(args.max_h, args.max_w)}")
+                name = item["filename"]
+                view = ds.metas[k][1]
+                for kind, t in (("depth_est", depth), ("confidence", conf)):
+                    path = os.path.join(args.outdir, name.format(kind, ".pfm"))
+                    os.makedirs(os.path.dirname(path), exist_ok=True)
+                    writer.submit(save_pfm, path, t.cpu().numpy())
+                if args.depth_png:
+                    # coloured on the device now; the writer thread makes the one copy to the host and encodes it
+                    writer.submit(depth_vis.save_png, os.path.join(args.outdir, name.format("depth_est", ".pfm")) + ".png", depth_vis.depth_colormap(depth)[0])
+                if resident:
+                    depth_maps[view], conf_maps[view] = depth, conf
+        views_done += len(ds)
+        f = fusion.TANKS_FILTER[args.split][scene]
+        fusion.filter_depth_tanks(os.path.join(args.testpath, args.split, scene), os.path.join(args.outdir, scene), ply, f["geo_pixel_thres"],
+                                  f["geo_depth_thres"], f["photo_thres"], img_wh, f["image_size"], f["geo_mask_thres"], args.num_view, scene,
+                                  device=str(device), depth_maps=depth_maps, conf_maps=conf_maps)
+        del depth_maps, conf_maps
+    if times:
+        warm = times[1:] or times
+        print(f"rank {rank}/{world}: {len(mine)} of {len(scenes)} scenes, {views_done} reference views, "
+              f"{1.0 / (sum(warm) / len(warm)):.1f} ref-views/s (model time), clouds under {args.plydir}")
 
 
 def score_scan(args, scan, device):
@@ -131,11 +223,20 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--testpath", default=None, help="folder of MVSNet-style scans (real data instead of synthetic scenes)")
     ap.add_argument("--testlist", default=None, help="text file, one scan name per line")
-    ap.add_argument("--num_view", type=int, default=5)
+    ap.add_argument("--dataset", choices=("dtu", "tanks"), default="dtu", help="tanks: the Tanks-and-Temples workflow (--split, --plydir, --scenes)")
+    ap.add_argument("--split", default="intermediate", help="tanks: intermediate or advanced")
+    ap.add_argument("--plydir", default=None, help="tanks: folder of the fused <scene>.ply files (default <outdir>/ply)")
+    ap.add_argument("--scenes", default=None, help="tanks: comma-separated scene names (default: every scene of the split)")
+    ap.add_argument("--resident-gb", type=float, default=8.0, help="tanks: hand a scene's depth and confidence maps to the fusion step on the device while "
+                                                                   "they fit in this many GB (M60: 313 views x 2 x 8.1 MB = 5.1 GB); 0 = read the PFM files back")
+    ap.add_argument("--depth-png", dest="depth_png", action="store_true", default=None,
+                    help="write the colour-mapped depth_est/<view>.pfm.png next to every depth map (on by default for tanks, off for dtu, as in the reference)")
+    ap.add_argument("--no-depth-png", dest="depth_png", action="store_false")
+    ap.add_argument("--num_view", type=int, default=None, help="default 5 (dtu), 7 (tanks)")
     ap.add_argument("--numdepth", type=int, default=192)
     ap.add_argument("--interval_scale", type=float, default=1.06)
-    ap.add_argument("--max_h", type=int, default=1200)
-    ap.add_argument("--max_w", type=int, default=1600)
+    ap.add_argument("--max_h", type=int, default=None, help="default 1200 (dtu), 1056 (tanks)")
+    ap.add_argument("--max_w", type=int, default=None, help="default 1600 (dtu), 1920 (tanks)")
     ap.add_argument("--io_threads", type=int, default=4, help="threads decoding input images ahead / writing outputs behind the GPU")
     ap.add_argument("--filter", action="store_true", help="fuse each scan's depth maps into <outdir>/<scan>.ply afterwards")
     ap.add_argument("--dtu-gt", default=None, help="DTU MVS_Data folder: after --filter, score each fused cloud (accuracy / completeness, "
@@ -158,6 +259,13 @@ def main(argv=None):
     ap.add_argument("--procs-per-gpu", type=int, default=1, help="worker processes per GPU: items are independent, two processes per GPU overlap "
                                                                  "each other's latency-bound phases (rc_mvsnet_amd/sharding.py)")
     args = ap.parse_args(argv)
+    tanks = args.dataset == "tanks"
+    for name, dtu_default, tanks_default in (("num_view", 5, 7), ("max_h", 1200, 1056), ("max_w", 1600, 1920), ("depth_png", False, True)):
+        if getattr(args, name) is None:
+            setattr(args, name, tanks_default if tanks else dtu_default)
+    if tanks:
+        args.plydir = args.plydir or os.path.join(args.outdir, "ply")
+        tanks_scenes(args)                                              # argument errors end here, before any rank starts or the network is built
     if args.dtu_gt and not args.filter:
         raise SystemExit("eval_driver: --dtu-gt scores the clouds of --filter; give both")
     nproc = args.gpus * args.procs_per_gpu
@@ -187,6 +295,8 @@ def main(argv=None):
     model.load_state_dict(sd, strict=True)
     model = model.to(device).eval()
 
+    if tanks:
+        return run_tanks(model, args, device, rank, world)              # no CPU path: on CPU tensors the first kernel wrapper raises
     if args.testpath:
         if device.type != "cuda":
             raise SystemExit("eval_driver: real data needs a GPU (the loader's image preparation has no CPU fallback)")

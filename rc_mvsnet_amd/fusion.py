@@ -164,14 +164,55 @@ def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, prob_thresho
     return xyz, rgb
 
 
+def _tanks_filter(sizes, geo_mask, photo, geo_pixel, geo_depth):
+    return {s: {"image_size": sizes[s], "geo_mask_thres": geo_mask[s], "photo_thres": photo[s], "geo_pixel_thres": geo_pixel[s],
+                "geo_depth_thres": geo_depth[s]} for s in sizes}
+
+
+# The per-scene settings of the reference's Tanks-and-Temples evaluation (eval_rcmvsnet_tanks.py:400-440 intermediate, :460-491
+# advanced; they sit under ``if __name__ == '__main__'`` there): TANKS_FILTER[split][scene] -> original image size (w, h), number of
+# consistent source views, confidence threshold, reprojection distance in pixels, relative depth difference.
+TANKS_FILTER = {
+    "intermediate": _tanks_filter(
+        {"Family": (1920, 1080), "Francis": (1920, 1080), "Horse": (1920, 1080), "Lighthouse": (2048, 1080), "M60": (2048, 1080),
+         "Panther": (2048, 1080), "Playground": (1920, 1080), "Train": (1920, 1080)},
+        {"Family": 6, "Francis": 8, "Horse": 4, "Lighthouse": 7, "M60": 6, "Panther": 7, "Playground": 7, "Train": 6},
+        {"Family": 0.9, "Francis": 0.8, "Horse": 0.8, "Lighthouse": 0.8, "M60": 0.9, "Panther": 0.9, "Playground": 0.85, "Train": 0.9},
+        {"Family": 0.75, "Francis": 1.0, "Horse": 1.25, "Lighthouse": 1.0, "M60": 0.75, "Panther": 1.0, "Playground": 1.0, "Train": 1.5},
+        {"Family": 0.01, "Francis": 0.01, "Horse": 0.01, "Lighthouse": 0.01, "M60": 0.005, "Panther": 0.01, "Playground": 0.01, "Train": 0.01}),
+    "advanced": _tanks_filter(
+        {"Auditorium": (1920, 1080), "Ballroom": (1920, 1080), "Courtroom": (1920, 1080), "Museum": (1920, 1080), "Palace": (1920, 1080),
+         "Temple": (1920, 1080)},
+        {"Auditorium": 3, "Ballroom": 4, "Courtroom": 3, "Museum": 4, "Palace": 5, "Temple": 3},
+        {"Auditorium": 0.7, "Ballroom": 0.8, "Courtroom": 0.8, "Museum": 0.8, "Palace": 0.9, "Temple": 0.8},
+        {"Auditorium": 4.0, "Ballroom": 4.0, "Courtroom": 3.0, "Museum": 4.0, "Palace": 4.0, "Temple": 4.0},
+        {"Auditorium": 0.005, "Ballroom": 0.005, "Courtroom": 0.005, "Museum": 0.01, "Palace": 0.005, "Temple": 0.01}),
+}
+
+
+def _resident(maps, view, dev, what):
+    """the (H,W) fp32 device tensor of ``view`` handed over by the caller, or None: then the PFM file is read"""
+    t = None if maps is None else maps.get(view)
+    if t is None:
+        return None
+    if t.dim() != 2 or t.dtype != torch.float32 or t.device != dev:
+        raise _lib.RcmvsError(f"filter_depth_tanks: {what} of view {view} must be an (H,W) fp32 tensor on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    return t.contiguous()
+
+
 def filter_depth_tanks(scan_folder, out_folder, plyfilename, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes,
-                       geo_mask_thres, n_views=None, scan="", device="cuda:0", save_masks=True, verbose=True):
+                       geo_mask_thres, n_views=None, scan="", device="cuda:0", save_masks=True, verbose=True, depth_maps=None,
+                       conf_maps=None):
     """eval_rcmvsnet_tanks.py:269-380, the Tanks-and-Temples form of filter_depth: pair.txt, cams_1/ and images/ live in
     ``scan_folder`` at the ORIGINAL image size ``image_sizes`` = (w, h); the depth maps under ``out_folder`` have the network
     size ``img_wh`` = (w, h), so the intrinsics' first two rows are rescaled and the colour image is resized (cv2.resize's
-    rule, on the device).  Same kernels as filter_depth.  Returns (xyz (n,3) fp32, rgb (n,3) uint8)."""
+    rule, on the device).  Same kernels as filter_depth.  depth_maps / conf_maps: optional {view: (H,W) fp32 tensor on ``device``},
+    the network's outputs still in HBM; where a view is present its PFM file is not read (PFM holds fp32 losslessly, so the
+    cloud is the same to the byte).  Returns (xyz (n,3) fp32, rgb (n,3) uint8)."""
     from .mvs_dataset import prepare_image
     dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
     pairs = scan_io.read_pair_file(os.path.join(scan_folder, "pair.txt"))
     views = sorted({v for ref, srcs in pairs for v in [ref] + list(srcs)})
     slot = {v: i for i, v in enumerate(views)}
@@ -182,7 +223,14 @@ def filter_depth_tanks(scan_folder, out_folder, plyfilename, geo_pixel_thres, ge
         K[0] *= img_wh[0] / ow
         K[1] *= img_wh[1] / oh
         cams[v] = (K, E)
-    depth_all = torch.from_numpy(np.stack([read_pfm(os.path.join(out_folder, "depth_est/{:0>8}.pfm".format(v)))[0] for v in views])).to(dev)
+    planes = []
+    for v in views:
+        t = _resident(depth_maps, v, dev, "depth")
+        if t is None:
+            t = torch.from_numpy(np.ascontiguousarray(read_pfm(os.path.join(out_folder, "depth_est/{:0>8}.pfm".format(v)))[0])).to(dev)
+        planes.append(t)
+    depth_all = torch.stack(planes)
+    del planes
     if tuple(depth_all.shape[1:]) != (img_wh[1], img_wh[0]):
         raise _lib.RcmvsError(f"filter_depth_tanks: depth maps are {tuple(depth_all.shape[1:])}, img_wh says {(img_wh[1], img_wh[0])}")
     if save_masks:
@@ -191,7 +239,9 @@ def filter_depth_tanks(scan_folder, out_folder, plyfilename, geo_pixel_thres, ge
     for ref, srcs in pairs:
         if len(srcs) > MAX_SRC:
             raise _lib.RcmvsError(f"filter_depth_tanks: view {ref} lists {len(srcs)} source views (at most {MAX_SRC})")
-        conf = torch.from_numpy(read_pfm(os.path.join(out_folder, "confidence/{:0>8}.pfm".format(ref)))[0]).to(dev)
+        conf = _resident(conf_maps, ref, dev, "confidence")
+        if conf is None:
+            conf = torch.from_numpy(np.ascontiguousarray(read_pfm(os.path.join(out_folder, "confidence/{:0>8}.pfm".format(ref)))[0])).to(dev)
         raw = np.array(Image.open(os.path.join(scan_folder, "images/{:0>8}.jpg".format(ref))), dtype=np.uint8)
         img = prepare_image(raw, (img_wh[1], img_wh[0]), dev, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)).permute(1, 2, 0).contiguous()
         mats = torch.from_numpy(fusion_matrices(cams[ref][0], cams[ref][1], [cams[s][0] for s in srcs], [cams[s][1] for s in srcs])).to(dev)

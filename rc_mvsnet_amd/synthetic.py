@@ -454,3 +454,37 @@ def write_dtu_train_folder(folder, scans, n_views, seed, hw=(512, 640), raw_hw=(
     with open(lst, "w") as f:
         f.write("".join(s + "\n" for s in scans))
     return lst
+
+
+# ----------------------------------------------------------------------------------------
+# depth maps for the colour-map tests and a Tanks-and-Temples tree for the evaluation driver
+# ----------------------------------------------------------------------------------------
+def depth_vis_map(H, W, seed=0, outliers=0.03, noise=0.25):
+    """One (H,W) fp32 depth map the way the network leaves it: the smooth surface of ``fusion_scan`` over the pixel grid plus
+    seeded noise, and a fraction ``outliers`` of far values (2x to 6x the depth), which is what makes the reference colour up to
+    the 95th percentile and not up to the maximum."""
+    rng = np.random.default_rng(seed)
+    ys, xs = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    d = _surface(xs * (640.0 / max(W, 1)), ys * (480.0 / max(H, 1))) + 0.3 * xs * (640.0 / max(W, 1)) + noise * rng.standard_normal((H, W))
+    if outliers > 0:
+        far = rng.random((H, W)) < outliers
+        d = np.where(far, d * (2.0 + 4.0 * rng.random((H, W))), d)
+    return d.astype(np.float32)
+
+
+def write_tanks_tree(root, split="intermediate", scenes=("Family", "Horse"), V=7, hw=(64, 96), orig_hw=(75, 100), seed=0, n_src=6,
+                     depth_line="425.0 935.0"):
+    """<root>/<split>/<scene>/{pair.txt, cams_1/, images/} for each scene (real scene names, tiny images): what
+    ``mvs_dataset.TanksDataset`` and ``fusion.filter_depth_tanks`` read.  The camera files hold the intrinsics at the ORIGINAL
+    image size (datasets/tanks.py divides their first two rows by 4 for the coarsest stage).  Returns {scene: scan}."""
+    import os
+    import shutil
+    out = {}
+    for i, scene in enumerate(scenes):
+        scan = tanks_fusion_scan(V=V, hw=hw, orig_hw=orig_hw, seed=seed + i, n_src=n_src)
+        folder = os.path.join(root, split, scene)
+        write_tanks_scan(scan, folder, depth_line=depth_line)
+        for sub in ("depth_est", "confidence"):                     # write_fusion_scan's network outputs are not part of a data folder
+            shutil.rmtree(os.path.join(folder, sub), ignore_errors=True)
+        out[scene] = scan
+    return out
