@@ -128,10 +128,28 @@ def test_k1_window_form_on_emulated_kernels(C, D, h, w, smooth, emu):
 def test_k1_forms_on_random_shapes_and_plane_tables(seed, emu):
     """Seeded fuzz of the three-view K1 forms (window 5 / 6, plane-pipelined 7) against the reference-order kernel: ragged image sizes down to
     2 x 2, 1-19 planes, 1-3 batch items, and plane tables that are smooth, rough, uniform, or cross z = 0 (taps dropped, non-finite
-    positions): same values to 2e-6 of the range and the same finite / non-finite pattern."""
+    positions): same values to 2e-6 of the range and the same finite / non-finite pattern; then the plane-pipelined form once more with 4, 5 or 7
+    views on the same shape and table.  Every form, and the reference-order kernel itself, is also held to the oracle at the voxels the oracle
+    calls well-conditioned."""
     import random
+    import test_gpu_parity as GP
+    from oracle import warp
     from rc_mvsnet_amd import ops
-    rnd = random.Random(seed)
+
+    def against_oracle(feats, rot, trans, planes, D, forms, what):
+        """Second comparator: oracle.warp.variance_volume on the very homographies the kernels got, 1e-5 of the range, at the voxels the oracle
+        itself calls well-conditioned (test_gpu_parity._k1_ill_conditioned)."""
+        V, (h, w) = feats.shape[1], feats.shape[2:4]
+        samples = planes[..., 0].unsqueeze(1) + torch.arange(D, dtype=torch.float32).view(1, D, 1, 1) * planes[..., 1].unsqueeze(1)
+        want = warp.variance_volume([feats[:, v].permute(0, 3, 1, 2) for v in range(V)], GP._k1_pm_from_homographies(rot, trans), samples)
+        ill = GP._k1_ill_conditioned(rot, trans, samples, h, w)
+        print(f"K1 fuzz {what}: ill-conditioned share {float(ill.float().mean()):.4f}")
+        assert float(ill.float().mean()) <= GP.K1_ILL_CAP, what          # (a draw past the cap would go nearly unchecked: re-seed it)
+        good = ~ill.unsqueeze(1).expand_as(want)
+        for name, v in forms.items():
+            assert float((v.permute(0, 4, 1, 2, 3) - want)[good].abs().max()) <= 1e-5 * max(1.0, float(want.abs().max())), (what, name)
+
+    rnd, rnd_v = random.Random(seed), random.Random(100 + seed)
     for n in range(10):
         C, B, D = rnd.choice([8, 16, 32]), rnd.choice([1, 1, 2, 3]), rnd.randint(1, 19)
         h, w = rnd.randint(2, 40), rnd.randint(2, 90)
@@ -155,6 +173,34 @@ def test_k1_forms_on_random_shapes_and_plane_tables(seed, emu):
             v = ops.warp_variance(feats, rot, trans, planes, D, variant=var)
             assert torch.equal(torch.isfinite(v), fin), (C, B, D, h, w, mode, var)
             assert float((torch.nan_to_num(v) - torch.nan_to_num(vref)).abs().max()) <= tol, (C, B, D, h, w, mode, var)
+            against_oracle(feats, rot, trans, planes, D, {2: vref, var: v}, (C, B, D, h, w, mode))
+        # the plane-pipelined form at the other view counts it is built for (3, 4 and 6 source views), same shape and plane table
+        V = rnd_v.choice([4, 5, 7])
+        feats = torch.randn(B, V, h, w, C, generator=torch.Generator().manual_seed(5000 + 1000 * seed + n))          # (its own generator: the three-view draws keep their values)
+        rot, trans = ops.compose_homography(synthetic.proj_matrices(B, V, h * 4, w * 4)["stage1"])
+        vref = ops.warp_variance(feats, rot, trans, planes, D, variant=2)
+        v = ops.warp_variance(feats, rot, trans, planes, D, variant=7)
+        fin = torch.isfinite(vref)
+        assert torch.equal(torch.isfinite(v), fin), (C, B, D, h, w, mode, V)
+        assert float((torch.nan_to_num(v) - torch.nan_to_num(vref)).abs().max()) <= 2e-6 * max(1.0, float(vref[fin].abs().max()) if bool(fin.any()) else 1.0), (C, B, D, h, w, mode, V)
+        against_oracle(feats, rot, trans, planes, D, {2: vref, 7: v}, (C, B, D, h, w, mode, V))
+
+
+def test_k1_border_cases_reach_every_edge_combination():
+    """The "border" cases of test_gpu_parity.test_warp_variance_hostile_geometry_vs_oracle put a sample on every combination of the eight border
+    positions in x and in y (-1, -1 + 2^-20, -0.5, 0, n-2, n-1, n-0.5, n) -- all 64 for EVERY view count, i.e. for every kernel instantiation
+    and every form (variants 0 / 1 / 2 run at every view count, 7 at V = 3, 4, 5, 7, the window forms 5 / 6 at V = 3).  No kernel runs here:
+    the oracle's coordinates alone."""
+    import test_gpu_parity as GP
+    seen = {V: set() for V in range(2, 8)}
+    for (mode, B, V, C, D, h, w, uniform, seed) in GP._k1_hostile_params():
+        if mode == "border":
+            _, _, rot, trans, _, samples = GP._k1_hostile_case(B, V, C, D, h, w, mode, seed)
+            got = GP._k1_border_combinations(*GP._k1_border_exact_positions(rot, trans, samples, h, w), h, w)
+            assert len(got) >= min(B * (V - 1), 25), (V, seed, len(got))
+            seen[V] |= got
+    for V, s in seen.items():
+        assert len(s) == 64, (V, sorted(set(range(64)) - s))
 
 
 def test_results_do_not_depend_on_the_thread_schedule(emu):

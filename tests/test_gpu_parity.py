@@ -89,6 +89,314 @@ def _k1_case(B, V, C, D, h, w, seed):
     return feats, pm, torch.stack((d0, dl), dim=-1)
 
 
+# ---- hostile geometry: planes behind the cameras, pz == 0, positions exactly on the image borders, huge / non-finite positions
+# translations by -1 put pixels 0, 1, n-1 on the positions -1, 0, n-2; by +1 pixels n-2, n-1 on n-1, n; the other three put pixel 0 / n-1 on -1 + 2^-20, -0.5, n-0.5:
+# five classes per axis reach all eight border positions, their 25 pairs all 64 (x edge, y edge) combinations
+K1_EDGE_SHIFTS = (-1.0, -1.0 + 2.0 ** -20, -0.5, 0.5, 1.0)
+K1_ILL_CAP = 0.02
+
+
+def _k1_pm_from_homographies(rot, trans):
+    """Projection matrices (B,V,2,4,4) whose oracle homographies are exactly rot (B,V-1,9) / trans (B,V-1,3): identity reference camera,
+    identity intrinsics, source extrinsic [R | t] (products with 0 and 1 only, so the oracle's fp32 matmul / inverse return them bit for bit)."""
+    B, n = rot.shape[:2]
+    pm = torch.zeros(B, n + 1, 2, 4, 4)
+    pm[:, :, 0] = torch.eye(4)
+    pm[:, :, 1, :3, :3] = torch.eye(3)
+    pm[:, 1:, 0, :3, :3] = rot.reshape(B, n, 3, 3)
+    pm[:, 1:, 0, :3, 3] = trans
+    return pm
+
+
+def _k1_translation(B, n, shifts):
+    """rot / trans of pure translations: rz * d + t2 = 1 whatever d, position = (x, y) * d + (sx, sy)."""
+    rot = torch.zeros(B, n, 9)
+    rot[..., 0] = 1.0
+    rot[..., 4] = 1.0
+    trans = torch.ones(B, n, 3)
+    trans[..., :2] = shifts
+    return rot, trans
+
+
+def _k1_hostile_case(B, V, C, D, h, w, mode, seed):
+    """Seeded K1 inputs on hostile geometry -> feats (list of V (B,C,h,w)), pm (B,V,2,4,4), rot (B,V-1,9), trans (B,V-1,3) -- the oracle's own
+    fp32 homographies of pm, bit for bit --, planes (B,h,w,2) and the oracle's samples (B,D,h,w).  Modes:
+      friendly  the synthetic cameras with planes at 425-525 mm (what _k1_case builds);
+      behind    the synthetic cameras, d0 in [-200, 200], delta ~ 40 N(0,1): pz changes sign along the sweep;
+      zero      view 1: pz = d - 8 with d = 8 - 2 j + 2 k, so pz == 0.0f exactly at plane k == j(x, y) (0 / 0 in column 0, +-x / 0 elsewhere);
+                view 2 (if any): rz row = 0 and t2 = 0, pz == 0 everywhere; further views: translations;
+      border    pure translations by (sx, sy) from K1_EDGE_SHIFTS, d = 1 (pixels of the top-left 2 x 2 block step d by 1 per plane: positions (x, y) * d + (sx, sy)):
+                every position is exact and lands on -1, -1 + 2^-20, -0.5, 0, w-2, w-1, w-0.5, w (and the same in y);
+      huge      positions (x, y) * d with |d| = 2^22 ... 2^40 (both sides of the kernels' |position| < 2^24 guard), +-inf, NaN and overflowing planes, delta = 0;
+      mixed     the synthetic cameras and a smooth in-range table with one- to three-pixel stripes of behind / zero-depth / huge / inf / NaN planes,
+                so that one tile and one wave hold live and dead lanes together."""
+    from oracle import warp
+    from rc_mvsnet_amd import synthetic
+    g = torch.Generator().manual_seed(seed)
+    n = V - 1
+    feats = [torch.randn(B, C, h, w, generator=g) for _ in range(V)]
+    if mode in ("friendly", "behind", "mixed"):
+        pm0 = synthetic.proj_matrices(B, V, h * 4, w * 4)["stage1"]
+        rt = [warp.compose_homography(pm0[:, v], pm0[:, 0]) for v in range(1, V)]
+        rot = torch.stack([r.reshape(B, 9) for r, _ in rt], dim=1)
+        trans = torch.stack([t for _, t in rt], dim=1)
+        rot = rot * (1.0 + 0.01 * torch.randn(B, n, 1, generator=g))          # a different homography per batch item
+    if mode == "friendly":
+        d0, dl = 425.0 + 100.0 * torch.rand(B, h, w, generator=g), 2.0 + 8.0 * torch.rand(B, h, w, generator=g)
+    elif mode == "behind":
+        d0, dl = -200.0 + 400.0 * torch.rand(B, h, w, generator=g), 40.0 * torch.randn(B, h, w, generator=g)
+    elif mode == "mixed":
+        yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+        d0 = (500.0 + 0.8 * xx + 0.5 * yy).expand(B, h, w) + 3.0 * torch.rand(B, h, w, generator=g)
+        dl = torch.full((B, h, w), 2.5)
+        stripes = ((-200.0, 40.0), (0.0, 0.0), (2.0 ** 30, 0.0), (-1e30, 1e29), (float("inf"), 0.0), (float("-inf"), 1.0), (float("nan"), 2.5), (150.0, float("nan")),
+                   (-60.0, 17.0))
+        for i, (a, s) in enumerate(stripes):
+            x0 = (1 + 5 * i) % w                                         # columns 1, 6, 11, ...: every 32- / 16- / 8-pixel tile row gets several
+            y0 = 8 if a in (-200.0, -60.0) else 0                    # (behind the cameras: from row 8 down, so that the upper tile rows keep the LDS-window path)
+            d0[:, y0:, x0:x0 + 1 + i % 3] = a
+            dl[:, y0:, x0:x0 + 1 + i % 3] = s
+        y0 = h // 2
+        d0[:, y0, ::2] = -100.0 + 200.0 * torch.rand(B, (w + 1) // 2, generator=g)        # half a row behind the cameras
+        dl[:, y0, ::2] = 30.0
+    elif mode == "zero":
+        yy, xx = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
+        j = ((xx + 2 * yy) % (D + 1)).float().expand(B, h, w)
+        d0, dl = 8.0 - 2.0 * j, torch.full((B, h, w), 2.0)
+        sh = torch.tensor([[K1_EDGE_SHIFTS[(seed + i) % 5], K1_EDGE_SHIFTS[(seed + 2 * i + 1) % 5]] for i in range(B * n)]).reshape(B, n, 2)
+        rot, trans = _k1_translation(B, n, sh)
+        rot[:, 0, 8], trans[:, 0, 2] = 1.0, -8.0
+        trans[:, 0, :2] = 0.0
+        if n > 1:
+            trans[:, 1, 2] = 0.0
+    elif mode == "border":
+        # (item, view) i of the case takes shift pair seed + i of the 25: x class p mod 5, y class (p div 5) mod 5 -- cases whose seeds follow
+        # each other walk all 25 pairs, i.e. all 64 (x edge, y edge) combinations, and one case reaches at least min(B (V-1), 25) of them
+        sh = torch.tensor([[K1_EDGE_SHIFTS[(seed + i) % 5], K1_EDGE_SHIFTS[((seed + i) // 5) % 5]] for i in range(B * n)]).reshape(B, n, 2)
+        rot, trans = _k1_translation(B, n, sh)
+        d0 = torch.ones(B, h, w)
+        dl = torch.zeros(B, h, w)
+        dl[:, :2, :2] = (torch.rand(B, 2, 2, generator=g) < 0.6).float()     # (x, y <= 1: (x, y) * d + 2^-20 stays within 24 bits)
+    elif mode == "huge":
+        rot, trans = _k1_translation(B, n, torch.zeros(B, n, 2))
+        e = torch.randint(22, 41, (B, h, w), generator=g).float()
+        sign = torch.where(torch.rand(B, h, w, generator=g) < 0.5, -1.0, 1.0)
+        d0 = sign * torch.exp2(e)
+        pick = torch.rand(B, h, w, generator=g)
+        d0 = torch.where(pick < 0.25, torch.ones(()), d0)                 # a quarter of the pixels stay in range
+        d0 = torch.where((pick >= 0.25) & (pick < 0.30), torch.full((), 2.0 ** 24) - 1.0, d0)       # the last float below the guard at x = 1
+        flat = d0.reshape(B, -1)
+        for i, v in enumerate((float("inf"), float("-inf"), float("nan"), 3e38, -3e38)):      # (+-3e38: (x, y) * d overflows from x = 2 on)
+            flat[:, (7 * i + 3) % (h * w)] = v
+        d0, dl = flat.reshape(B, h, w), torch.zeros(B, h, w)
+    else:
+        raise ValueError(mode)
+    planes = torch.stack((d0, dl), dim=-1).contiguous()
+    pm = _k1_pm_from_homographies(rot, trans)
+    for v in range(1, V):
+        r, t = warp.compose_homography(pm[:, v], pm[:, 0])
+        assert torch.equal(r.reshape(B, 9), rot[:, v - 1]) and torch.equal(t, trans[:, v - 1])
+    k = torch.arange(D, dtype=torch.float32).reshape(1, D, 1, 1)
+    samples = planes[..., 0].unsqueeze(1) + k * planes[..., 1].unsqueeze(1)
+    return feats, pm, rot.contiguous(), trans.contiguous(), planes, samples
+
+
+def _k1_positions(rot, trans, samples, h, w, dtype=torch.float32):
+    """The oracle's sampling positions of every source view: ix, iy (B,V-1,D,h,w), the whole chain evaluated in dtype on the fp32 inputs."""
+    from oracle import warp
+    B, n = rot.shape[:2]
+    pos = [warp.warp_coords(rot[:, v].reshape(B, 3, 3).to(dtype), trans[:, v].to(dtype), samples.to(dtype), h, w) for v in range(n)]
+    return torch.stack([p[0] for p in pos], dim=1), torch.stack([p[1] for p in pos], dim=1)
+
+
+def _k1_ill_conditioned(rot, trans, samples, h, w):
+    """(B,D,h,w) bool, decided from the oracle alone: a voxel where, for some source view, the position of the fp32 chain or of the fp64 chain
+    (same fp32 inputs) lies inside [-2, w+1] x [-2, h+1] and the two differ by more than 1/64 pixel -- the position is a discontinuous
+    function of the last bit of pz there, and one rounding anywhere upstream legitimately moves the sample."""
+    ix, iy = _k1_positions(rot, trans, samples, h, w)
+    jx, jy = _k1_positions(rot, trans, samples, h, w, torch.float64)
+
+    def inside(x, y):
+        return (x >= -2) & (x <= w + 1) & (y >= -2) & (y <= h + 1)           # False for NaN / inf
+    same = ((ix.double() - jx).abs() <= 1.0 / 64) & ((iy.double() - jy).abs() <= 1.0 / 64)
+    return ((inside(ix, iy) | inside(jx, jy)) & ~same).any(dim=1)
+
+
+def _k1_ill_share(mode, rot, trans, samples, h, w):
+    ill = _k1_ill_conditioned(rot, trans, samples, h, w)
+    share = float(ill.float().mean())
+    print(f"K1 hostile {mode}: ill-conditioned share {share:.4f} ({int(ill.sum())} of {ill.numel()} voxels)")
+    assert share <= (0.0 if mode in ("border", "huge") else K1_ILL_CAP), (mode, share)
+    return ill
+
+
+def _k1_closed_form_border(feats, X, Y):
+    """Variance volume (B,C,D,h,w) of a "border" case in closed form, float64, from its exact positions X, Y (B,V-1,D,h,w): the sample of a view
+    is a shifted copy of the source with the two rows / columns of the footprint weighted 1 - f and f, texels outside the image counting
+    zero (read from a zero-padded copy: no masks, no clamps)."""
+    V = len(feats)
+    B, C, h, w = feats[0].shape
+    D = X.shape[2]
+    ref = feats[0].double().unsqueeze(2).expand(B, C, D, h, w)
+    s, q = ref.clone(), ref ** 2
+    PAD = 4
+    bi = torch.arange(B).reshape(B, 1, 1, 1)
+    for v in range(1, V):
+        x, y = X[:, v - 1], Y[:, v - 1]
+        big = torch.zeros(B, h + 2 * PAD, w + 2 * PAD, C, dtype=torch.float64)
+        big[:, PAD:PAD + h, PAD:PAD + w] = feats[v].double().permute(0, 2, 3, 1)
+        x0, y0 = x.floor(), y.floor()
+        fx, fy = x - x0, y - y0
+        xi = (x0.clamp(-PAD, w + PAD - 2) + PAD).long()
+        yi = (y0.clamp(-PAD, h + PAD - 2) + PAD).long()
+        val = 0
+        for dy, wy in ((0, 1 - fy), (1, fy)):
+            for dx, wx in ((0, 1 - fx), (1, fx)):
+                val = val + big[bi, yi + dy, xi + dx] * (wx * wy).unsqueeze(-1)           # (B,D,h,w,C)
+        far = ((x < -2) | (x > w + 1) | (y < -2) | (y > h + 1)).unsqueeze(-1)               # (clamped above: nothing of the image in reach)
+        val = torch.where(far, torch.zeros((), dtype=torch.float64), val).permute(0, 4, 1, 2, 3)
+        s, q = s + val, q + val ** 2
+    return q / V - (s / V) ** 2
+
+
+def _k1_route(V, C, uniform):
+    """The debug variant k1_production_variant (csrc/warp_variance.hip) names for a hinted call."""
+    nsrc = V - 1
+    if nsrc == 2:
+        return 5 if uniform else (7 if C == 8 else 0)
+    if nsrc in (3, 6):
+        return 7
+    if nsrc == 4:
+        return 1 if (C == 16 and not uniform) else 7
+    return 0
+
+
+def _k1_hostile_params():
+    """(mode, B, V, C, D, h, w, uniform, seed): every (source views, C, hint) class k1_production_variant distinguishes, once per mode, on ragged
+    shapes: 2 x 2, w == 2, h == 2, one dimension just past a tile (4 rows; 8 / 16 / 32 pixels wide at C = 32 / 16 / 8), D not a multiple of 4 or
+    8, B in {1, 2, 3}.  "border" has, for EVERY view count, as many three-item cases as it takes to walk the 25 shift pairs (seed = the first
+    pair of the case), so that every kernel instantiation -- and with it every form: the window form at V = 3, the plane-pipelined form at
+    V = 3, 4, 5, 7, the compile-time and the run-time view loops of the two-phase kernel -- meets all 64 (x edge, y edge) combinations."""
+    routes = [(3, 8, False), (3, 16, False), (3, 32, True), (3, 8, True), (4, 8, False), (4, 32, True), (7, 16, False), (7, 8, True),
+              (5, 16, False), (5, 16, True), (5, 8, False), (2, 32, False), (6, 8, False), (6, 32, True), (2, 16, True)]
+    shapes = [(2, 2), (5, 9), (2, 17), (9, 2), (4, 33), (7, 12), (3, 5), (13, 20), (5, 34), (6, 31), (8, 8)]
+    # "mixed": room for the stripes and live taps between them, widths that leave a ragged last tile in every C class (8 / 16 / 32 pixels)
+    mixed = [(9, 20), (9, 21), (13, 25), (9, 37), (9, 34), (10, 31), (13, 20), (9, 33), (11, 27), (9, 41)]
+    # "border": w - 1 and h - 1 powers of two up to 16, so that grid_sample's normalise / un-normalise round trip (u / ((w-1)/2) - 1, + 1, / 2,
+    # * (w-1)) is exact down to the 2^-20 of the position -1 + 2^-20 and the samples sit ON the borders, not an ulp beside them
+    exact = [(2, 2), (5, 9), (2, 17), (9, 2), (3, 5), (17, 9), (5, 17), (9, 3), (3, 3), (5, 2), (9, 17)]
+    depths = [1, 3, 5, 7, 9, 11, 6]
+    out = []
+    for mi, mode in enumerate(("behind", "zero", "huge", "mixed")):
+        for ri, (V, C, uniform) in enumerate(routes):
+            i = mi * 4 + ri
+            h, w = mixed[i % len(mixed)] if mode == "mixed" else shapes[i % len(shapes)]
+            out.append((mode, 1 + i % 3, V, C, depths[i % len(depths)], h, w, uniform, 11 + V + C))
+    i = 0
+    for V in (2, 3, 4, 5, 6, 7):
+        classes = [(C, u) for (v, C, u) in routes if v == V]
+        for j in range(-(-25 // (3 * (V - 1)))):
+            C, uniform = classes[j % len(classes)]
+            h, w = exact[i % len(exact)]
+            out.append(("border", 3, V, C, depths[i % len(depths)], h, w, uniform, j * 3 * (V - 1)))
+            i += 1
+    return out
+
+
+@pytest.mark.parametrize("mode,B,V,C,D,h,w,uniform,seed", _k1_hostile_params())
+def test_warp_variance_hostile_geometry_vs_oracle(hip, mode, B, V, C, D, h, w, uniform, seed):
+    """Every K1 forward form on hostile geometry (_k1_hostile_case) against oracle.warp.variance_volume: the production call, the debug variants
+    that accept the view count (0, 1, 2; 7 for 2 / 3 / 4 / 6 source views; 5 / 6 for two), 1e-5 of the range against the oracle, 2e-6 between a
+    fast form and variant 2, variant 0 == variant 2 bit for bit, the hinted call == the variant the routing table names, and no non-finite
+    output anywhere (the oracle has none: dead taps contribute zero).  At ill-conditioned voxels (_k1_ill_conditioned; at most 2 % of a case,
+    none in "border" / "huge") only: finite, |var| <= max|feat|^2, and the forms agree with each other.  "border" is also held to its closed
+    form.  With d0 in [-200, 200] and delta ~ 40 N(0,1) as specified, the ill-conditioned share of "behind" -- and of every other case of
+    this list -- is 0 (printed), so its ranges are not narrowed; it also means that the relaxed assertions for ill-conditioned voxels are
+    not exercised by these inputs.  A translation gives one (sx, sy) pair per (item, view) and a pair reaches the border combinations of its
+    two shift classes only, so one case reaches at least min(B (V-1), 25) of the 64 combinations (asserted here) and the cases of ONE view
+    count together all 64 (asserted from the oracle's coordinates in test_emu_kernels_cpu.py::test_k1_border_cases_reach_every_edge_combination).
+    The window forms must really take the window path on some tiles of the "mixed" cases (live and dead lanes in one wave's min / max)."""
+    from oracle import warp
+    feats, pm, rot, trans, planes, samples = _k1_hostile_case(B, V, C, D, h, w, mode, seed)
+    ill = _k1_ill_share(mode, rot, trans, samples, h, w)                       # before anything runs on the device
+    ref = warp.variance_volume(feats, pm, samples)                            # (B,C,D,h,w)
+    assert torch.isfinite(ref).all()
+    fmax = max(float(f.abs().max()) for f in feats)
+    good = ~ill.unsqueeze(1).expand_as(ref)
+    f_cl = gpu(torch.stack([f.permute(0, 2, 3, 1) for f in feats], dim=1))
+    args = (f_cl, gpu(rot), gpu(trans), gpu(planes), D)
+    forms = {"call": hip.warp_variance(*args, uniform_planes=uniform)}
+    for var in (0, 1, 2):
+        forms[var] = hip.warp_variance(*args, variant=var)
+    if V - 1 in (2, 3, 4, 6):
+        forms[7] = hip.warp_variance(*args, variant=7)
+    if V == 3:
+        for var in (5, 6):
+            forms[var], blocks, on_window = hip.warp_variance_win(*args, variant=var)
+            print(f"K1 hostile {mode} B={B} V={V} C={C} D={D} {h}x{w} form {var}: {on_window} of {blocks} tiles on the window path")
+            assert 0 < blocks and on_window <= blocks
+            assert on_window > 0 or mode != "mixed"
+    forms = {k: v.cpu().permute(0, 4, 1, 2, 3) for k, v in forms.items()}
+    tol = 1e-5 * max(1.0, float(ref.abs().max()))
+    vref = forms[2]
+    for name, v in forms.items():
+        assert torch.isfinite(v).all(), (name, int((~torch.isfinite(v)).sum()))
+        err = float(((v - ref).abs() * good).max())
+        errv = float((v - vref).abs().max())
+        print(f"K1 hostile {mode} B={B} V={V} C={C} D={D} {h}x{w} form {name}: max|d| oracle {err:.3e} (tol {tol:.3e}), variant 2 {errv:.3e}")
+        assert err <= tol, (name, err)
+        assert errv <= 2e-6 * max(1.0, float(vref.abs().max())), (name, errv)
+        assert float(v.abs().max()) <= fmax * fmax * (1 + 1e-6), name
+    assert torch.equal(forms[0], forms[2])
+    assert torch.equal(forms["call"], forms[_k1_route(V, C, uniform)]), _k1_route(V, C, uniform)
+    if mode == "zero":          # the case hits what it claims: non-finite positions exactly where d == 8 (view 1), everywhere (view 2)
+        ix, iy = _k1_positions(rot, trans, samples, h, w)
+        dead = ~(torch.isfinite(ix) & torch.isfinite(iy))
+        assert torch.equal(dead[:, 0], samples == 8.0) and bool(dead[:, 0].any()) and (V < 3 or bool(dead[:, 1].all()))
+    if mode == "border":
+        ix, iy = _k1_border_exact_positions(rot, trans, samples, h, w)
+        reached = len(_k1_border_combinations(ix, iy, h, w))
+        print(f"K1 hostile border B={B} V={V} {h}x{w} pairs {seed}..{seed + B * (V - 1) - 1}: {reached} of 64 (x edge, y edge) combinations")
+        assert reached >= min(B * (V - 1), 25)
+        closed = _k1_closed_form_border(feats, ix, iy)
+        for name, v in forms.items():
+            assert float((v - closed).abs().max()) <= tol, ("closed form", name)
+
+
+def _k1_border_exact_positions(rot, trans, samples, h, w):
+    """Positions of a "border" case, asserted exact wherever a sample can reach the image: the oracle's fp32 chain == its fp64 chain ==
+    (x, y) * d + (sx, sy)."""
+    ix, iy = _k1_positions(rot, trans, samples, h, w)
+    jx, jy = _k1_positions(rot, trans, samples, h, w, torch.float64)
+    yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float64), torch.arange(w, dtype=torch.float64), indexing="ij")
+    d = samples.double().unsqueeze(1)
+    B, n = trans.shape[:2]
+    X = xx * d + trans[..., 0].double().reshape(B, n, 1, 1, 1)
+    Y = yy * d + trans[..., 1].double().reshape(B, n, 1, 1, 1)
+    near = (X >= -2) & (X <= w + 1) & (Y >= -2) & (Y <= h + 1)          # (far out, (x, y) * d + 2^-20 needs more than 24 bits: nothing is sampled there)
+    for a, b in ((ix.double(), X), (iy.double(), Y), (jx, X), (jy, Y)):
+        assert torch.equal(a[near], b[near])
+    assert not bool(((ix >= -1.5) & (ix <= w + 0.5) & (iy >= -1.5) & (iy <= h + 0.5) & ~near).any())
+    return X, Y
+
+
+def _k1_border_combinations(ix, iy, h, w):
+    """The (x edge, y edge) pairs a set of exact positions lands on: edges -1, -1 + 2^-20, -0.5, 0, n-2, n-1, n-0.5, n."""
+    def edge(p, n):
+        e = torch.full(p.shape, -1, dtype=torch.long)
+        for i, v in enumerate((-1.0, -1.0 + 2.0 ** -20, -0.5, 0.0, n - 2.0, n - 1.0, n - 0.5, float(n))):
+            e = torch.where((p == v) & (e < 0), torch.full((), i), e)          # (n == 2: 0 is also n-2; the first name wins, both below count)
+        return e
+    ex, ey = edge(ix, w), edge(iy, h)
+    ok = (ex >= 0) & (ey >= 0)
+    out = set((8 * ex[ok] + ey[ok]).unique().tolist())
+    if w == 2:
+        out |= {c + 8 for c in out if c // 8 == 3}
+    if h == 2:
+        out |= {c + 1 for c in out if c % 8 == 3}
+    return out
+
+
 @pytest.mark.parametrize("B,V,C,D,h,w,uniform", [(1, 3, 32, 8, 16, 20, False), (2, 3, 16, 16, 24, 40, False), (1, 5, 8, 8, 32, 48, False),
                                                  (1, 2, 32, 5, 9, 13, False), (1, 7, 8, 12, 10, 70, False),
                                                  # the production kernels, each against the oracle directly (what a hinted call runs: csrc/warp_variance.hip,
@@ -208,7 +516,8 @@ def test_warp_variance_variants_agree(hip):
     (variant 1) stays within 2e-6 relative."""
     from rc_mvsnet_amd import synthetic
     for (C, D, h, w, V) in ((32, 16, 20, 37, 3), (16, 8, 33, 50, 4), (8, 24, 30, 70, 2), (8, 8, 20, 40, 7),
-                            (16, 16, 18, 30, 5), (32, 8, 12, 20, 5), (8, 12, 64, 96, 3), (32, 8, 9, 11, 7), (16, 8, 14, 22, 7)):
+                            (16, 16, 18, 30, 5), (32, 8, 12, 20, 5), (8, 12, 64, 96, 3), (32, 8, 9, 11, 7), (16, 8, 14, 22, 7),
+                            (8, 12, 10, 36, 6), (32, 11, 13, 18, 6)):          # 5 source views: the general path, two LDS chunks at C = 8
         g = torch.Generator().manual_seed(C + V)
         feats = gpu(torch.randn(2, V, h, w, C, generator=g))
         pm = gpu(synthetic.proj_matrices(2, V, h * 4, w * 4)["stage1"])
@@ -1653,6 +1962,138 @@ def test_warp_variance_backward_vs_oracle_autograd(hip, C, V, D, h, w, with_nore
     err = rel_err(got, ref_grads)
     print(f"K1 bwd C={C} V={V}: rel err {err:.2e}")
     assert err < 2e-5
+    # the forward outputs of the autograd Function are the kernels' own, bit for bit
+    with torch.no_grad():
+        assert torch.equal(var_g if with_noref else out, hip.warp_variance(f_gpu.detach(), rot, trans, gpu(planes), D))
+        if with_noref:
+            assert torch.equal(noref_g, hip.warp_noref(f_gpu.detach(), imgs_cl, rot, trans, gpu(planes), D, False))
+
+
+def _k1_noref_params():
+    out = []
+    for i, (V, C) in enumerate([(2, 8), (3, 16), (4, 32), (5, 8), (7, 16), (3, 8), (4, 16), (5, 32), (7, 8), (2, 32), (3, 32), (7, 32), (2, 16), (4, 8), (5, 16)]):
+        mode = ("friendly", "mixed", "border")[i % 3]
+        h, w = [(9, 20), (11, 23), (5, 9)][i % 3] if mode != "border" else [(5, 9), (2, 17), (9, 2), (3, 3), (17, 5)][i // 3]
+        out.append((mode, 1 + i % 2, V, C, (3, 5, 2, 7)[i % 4], h, w))
+    return out
+
+
+@pytest.mark.parametrize("mode,B,V,C,D,h,w", _k1_noref_params())
+def test_warp_noref_vs_oracle(hip, mode, B, V, C, D, h, w):
+    """rcmvs_warp_noref_fwd (the train variant's extra output) against oracle.warp.volume_feature_no_ref at the kernel level: the 3 (V-1) warped
+    RGB channels and the C source-only-variance channels, each within 1e-5 of its range, layout (B, 3(V-1)+C, D, h, w), for the training form
+    and for the eval-mode in-place-square quirk (square_first), on a friendly case and on the "mixed" and "border" hostile modes."""
+    from oracle import warp
+    feats, pm, rot, trans, planes, samples = _k1_hostile_case(B, V, C, D, h, w, mode, 5 + V + C)
+    ill = _k1_ill_share(mode, rot, trans, samples, h, w)
+    g = torch.Generator().manual_seed(V)
+    imgs = torch.rand(V, B, 3, h, w, generator=g)
+    f_cl = gpu(torch.stack([f.permute(0, 2, 3, 1) for f in feats], dim=1))
+    i_cl = gpu(imgs.permute(1, 0, 3, 4, 2))
+    nrgb = 3 * (V - 1)
+    good = ~ill.unsqueeze(1)
+    outs = {}
+    for square_first in (False, True):
+        ref = warp.volume_feature_no_ref(feats, imgs, pm, samples, training=not square_first)
+        got = outs[square_first] = hip.warp_noref(f_cl, i_cl, gpu(rot), gpu(trans), gpu(planes), D, square_first).cpu()
+        assert got.shape == ref.shape == (B, nrgb + C, D, h, w)
+        assert torch.isfinite(ref).all() and torch.isfinite(got).all()
+        for name, sl in (("rgb", slice(0, nrgb)), ("var", slice(nrgb, nrgb + C))):
+            err = float(((got[:, sl] - ref[:, sl]).abs() * good).max())
+            tol = 1e-5 * max(1.0, float(ref[:, sl].abs().max()))
+            print(f"K1 no-ref {mode} B={B} V={V} C={C} square_first={square_first} {name}: max|d| {err:.3e} (tol {tol:.3e})")
+            assert err <= tol, (name, square_first, err)
+    assert torch.equal(outs[False][:, :nrgb], outs[True][:, :nrgb]) and not torch.equal(outs[False][:, nrgb:], outs[True][:, nrgb:])
+
+
+def _k1_bwd_check(hip, mode, B, V, C, D, h, w, with_noref, seed, variant2=False):
+    """K1 backward against float64 autograd through the oracle's op graph (sampling positions from the fp32 chain), B items with their own planes,
+    homographies and gradients.  Outside "border", grad_var / grad_noref are zeroed at ill-conditioned voxels on both sides."""
+    from oracle import warp as ow
+    feats, pm, rot, trans, planes, samples = _k1_hostile_case(B, V, C, D, h, w, mode, seed)
+    ill = _k1_ill_share(mode, rot, trans, samples, h, w)
+    gen = torch.Generator().manual_seed(seed + 1)
+    keep = (~ill).float()
+    gvar = torch.randn(B, D, h, w, C, generator=gen) * keep.unsqueeze(-1)
+    gnr = torch.randn(B, 3 * (V - 1) + C, D, h, w, generator=gen) * keep.unsqueeze(1)
+    imgs = torch.rand(B, V, 3, h, w, generator=gen)
+    ix, iy = _k1_positions(rot, trans, samples, h, w)
+    f64 = [f.double().requires_grad_(True) for f in feats]
+    warped = [ow.bilinear_gather_zeros(f64[v], ix[:, v - 1].double(), iy[:, v - 1].double()) for v in range(1, V)]
+    ref = f64[0].unsqueeze(2).expand(-1, -1, D, -1, -1)
+    s = ref + sum(warped)
+    q = ref ** 2 + sum(t ** 2 for t in warped)
+    loss = ((q / V - (s / V) ** 2).permute(0, 2, 3, 4, 1) * gvar.double()).sum()
+    if with_noref:
+        sn, qn = sum(warped), sum(t ** 2 for t in warped)
+        loss = loss + ((qn / V - (sn / V) ** 2) * gnr[:, -C:].double()).sum()
+    loss.backward()
+    want = torch.stack([f.grad.permute(0, 2, 3, 1) for f in f64], dim=1).float()          # (B,V,h,w,C)
+    f_gpu = gpu(torch.stack([f.permute(0, 2, 3, 1) for f in feats], dim=1)).requires_grad_(True)
+    dev = (gpu(rot), gpu(trans), gpu(planes))
+    out = hip.WarpVarianceFn.apply(f_gpu, *dev, D, gpu(imgs.permute(0, 1, 3, 4, 2)) if with_noref else None)
+    if with_noref:
+        (out[0] * gpu(gvar)).sum().add((out[1] * gpu(gnr)).sum()).backward()
+    else:
+        (out * gpu(gvar)).sum().backward()
+    got = f_gpu.grad.cpu()
+    assert torch.isfinite(got).all()
+    err = rel_err(got, want)
+    print(f"K1 bwd {mode} B={B} V={V} C={C} D={D} {h}x{w} noref={with_noref}: rel err {err:.2e}")
+    assert err < 2e-5
+    # texels of the source views that no in-image tap of a finite position touches: exactly zero
+    fin = torch.isfinite(ix) & torch.isfinite(iy)
+    x0, y0 = torch.where(fin, ix, torch.full_like(ix, -10.0)).floor().long(), torch.where(fin, iy, torch.full_like(iy, -10.0)).floor().long()
+    hits = torch.zeros(B, V - 1, h * w, dtype=torch.int32)
+    for dy in (0, 1):
+        for dx in (0, 1):
+            xx, yy = x0 + dx, y0 + dy
+            ok = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h) & (keep.unsqueeze(1) > 0)
+            lin = (yy.clamp(0, h - 1) * w + xx.clamp(0, w - 1)).reshape(B, V - 1, -1)
+            hits.scatter_add_(2, lin, ok.reshape(B, V - 1, -1).int())
+    touched = hits > 0
+    untouched = ~touched.reshape(B, V - 1, h, w)
+    assert bool((got[:, 1:][untouched] == 0).all())
+    print(f"K1 bwd {mode}: {int(untouched.sum())} of {untouched.numel()} source texels untouched, all exactly zero")
+    if variant2:                # the debug entry without run-length merging: the same sums in another order
+        gv = gpu(gvar)
+        gn = gpu(gnr[:, -C:].permute(0, 2, 3, 4, 1)) if with_noref else None
+        f_in = f_gpu.detach()
+        prod = hip.warp_variance_bwd(f_in, *dev, gv, gn).cpu()
+        nomerge = hip.warp_variance_bwd(f_in, *dev, gv, gn, variant=2).cpu()
+        bound = 1e-5 * max(1e-6, float(prod.abs().max()))
+        assert float((prod - got).abs().max()) <= bound              # (the same kernel twice: float atomics, unordered)
+        assert float((nomerge - prod).abs().max()) <= bound
+    return got
+
+
+@pytest.mark.parametrize("mode,B,V,C,D,h,w,with_noref", [
+    # batch items with their own planes, homographies and gradients (blockIdx.y > 0)
+    ("friendly", 2, 3, 16, 5, 9, 20, True), ("friendly", 3, 4, 8, 3, 7, 33, False), ("friendly", 2, 4, 32, 6, 10, 12, True), ("friendly", 3, 3, 8, 7, 5, 40, True),
+    # 5 / 6 source views: the instantiation without run-length merging
+    ("friendly", 1, 6, 8, 5, 9, 20, True), ("friendly", 1, 7, 32, 3, 9, 12, True), ("friendly", 2, 6, 32, 4, 6, 10, False), ("friendly", 1, 7, 8, 6, 8, 34, False),
+    # C = 8 with 4 / 6 source views: 69 632 / 102 400 bytes of dynamic LDS, past the 64 KiB default limit
+    ("friendly", 1, 5, 8, 5, 9, 36, True), ("friendly", 2, 7, 8, 3, 5, 20, True), ("mixed", 1, 5, 8, 6, 9, 34, False),
+    # hostile geometry, w == 2 and h == 2 among the sizes, with and without grad_noref
+    ("border", 1, 3, 8, 5, 5, 9, True), ("border", 2, 4, 16, 3, 2, 17, False), ("border", 1, 3, 32, 7, 9, 2, True), ("border", 3, 2, 8, 4, 2, 2, True),
+    ("border", 1, 5, 16, 6, 3, 5, False), ("border", 2, 7, 8, 3, 17, 9, True), ("border", 1, 4, 8, 9, 3, 3, False),
+    ("mixed", 2, 3, 16, 5, 9, 20, True), ("mixed", 1, 4, 8, 7, 11, 33, False), ("mixed", 3, 3, 32, 3, 9, 21, True), ("mixed", 1, 7, 16, 5, 9, 20, False),
+    ("behind", 2, 3, 8, 6, 7, 12, True), ("behind", 1, 4, 32, 5, 2, 9, False), ("behind", 1, 3, 16, 9, 13, 2, True), ("behind", 3, 5, 16, 3, 6, 31, True),
+    ("zero", 2, 3, 8, 5, 6, 7, True), ("huge", 1, 4, 16, 3, 5, 9, True)])
+def test_warp_variance_backward_branches(hip, mode, B, V, C, D, h, w, with_noref):
+    """The branches of the K1 backward that test_warp_variance_backward_vs_oracle_autograd (B = 1, V <= 5, friendly geometry) never runs,
+    same float64-autograd comparator and the same 2e-5 bound: blockIdx.y > 0 (the b * nsrc, b * V * hw * C, b * D * hw strides), NM = 0
+    (5 / 6 source views), more than 64 KiB of dynamic LDS, and the run-length merge on border footprints whose clamped offsets coincide
+    (o.x == o.y at xi == -1 / w-1, o.x == o.z at yi == -1 / h-1; w == 2, h == 2).  Texels no live tap touches keep exactly zero."""
+    _k1_bwd_check(hip, mode, B, V, C, D, h, w, with_noref, 31 + V + C)
+
+
+@pytest.mark.parametrize("mode,V,C,h,w", [("friendly", 2, 8, 7, 9), ("friendly", 3, 16, 9, 20), ("border", 4, 8, 5, 9), ("mixed", 5, 32, 9, 20), ("border", 3, 8, 2, 2),
+                                          ("border", 2, 16, 9, 2), ("mixed", 4, 16, 9, 24), ("friendly", 5, 8, 6, 33)])
+def test_warp_variance_backward_without_merging_equals_production(hip, mode, V, C, h, w):
+    """rcmvs_debug_warp_variance_bwd variant 2 (forces the instantiation without run-length merging) against the production backward, V = 2 ... 5:
+    equal up to summation order (1e-5 of max|g|), and both against float64 autograd."""
+    _k1_bwd_check(hip, mode, 2, V, C, 6, h, w, True, 57 + V + C, variant2=True)
 
 
 def test_cascade_batch_two_equals_two_singles(hip, monkeypatch):
