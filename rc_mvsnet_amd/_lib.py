@@ -3,143 +3,102 @@
 The library is built in-tree by ``__graft_entry__.build()`` (hipcc --offload-arch=gfx950).
 There is no fallback: if the shared object is missing or a call fails, an exception is raised.
 """
+import ast
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librcmvs_hip.so")
-REQUIRED_VERSION = 106      # RCMVS_VERSION of include/rcmvs.h this binding was written against (106: rcmvs_conv2d_stem_fwd)
 CSRC = os.path.join(_HERE, "csrc")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "rcmvs.h")
-
-_p = ctypes.c_void_p
-_i = ctypes.c_int
-_f = ctypes.c_float
-_ll = ctypes.c_longlong
-_d = ctypes.c_double
-
-# name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/rcmvs.h
-SIGNATURES = {
-    "rcmvs_version": [],
-    "rcmvs_last_error_string": [],
-    "rcmvs_nchw_to_nhwc": [_p, _p, _i, _i, _ll, _p],
-    "rcmvs_nhwc_to_nchw": [_p, _p, _i, _i, _ll, _p],
-    "rcmvs_compose_homography": [_p, _p, _p, _i, _i, _p],
-    "rcmvs_compose_homography_stages": [_p, _p, _p, _p, _i, _p, _p, _i, _i, _p, ctypes.c_longlong, _p],
-    "rcmvs_hypothesis_planes": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p],
-    "rcmvs_warp_variance_fwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_debug_warp_variance_fwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_warp_variance_hint_fwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_warp_variance_timed_fwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p],
-    "rcmvs_debug_warp_variance_win_fwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p],
-    "rcmvs_absmax_fwd": [_p, _ll, _i, _p, _p],
-    "rcmvs_conv3d_scaled_fwd": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_deconv3d_scaled_fwd": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_conv11_prob_fwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "rcmvs_softmax_head_fwd": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "rcmvs_conv2d_s2d_fwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_warp_variance_bwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_debug_warp_variance_bwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_resize_planes_bwd": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_composite_bwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p],
-    "rcmvs_point_feats_bwd": [_p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "rcmvs_inverse_warp": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
-    "rcmvs_unsup_loss_fwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "rcmvs_unsup_loss_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "rcmvs_masked_sl1_fwd": [_p, _p, _p, _p, _ll, _p],
-    "rcmvs_masked_sl1_bwd": [_p, _p, _p, _p, _p, _p, _ll, _p],
-    "rcmvs_fuse_view": [_p, _i, _p, _p, _p, _p, _f, _i, _d, _f, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
-    "rcmvs_compact_points": [_p, _p, _p, _p, _p, _p, _ll, _p],
-    "rcmvs_prepare_image": [_p, _p, _i, _i, _i, _i, _p, _p, _p],
-    "rcmvs_resize_rgb_cl": [_p, _p, _i, _i, _i, _i, _i, _p],
-    "rcmvs_conv2d_pair_weight_floats": [],
-    "rcmvs_pack_conv2d_pair": [_p, _p, _p, _p],
-    "rcmvs_conv2d_pair_fwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "rcmvs_conv2d_tile_weight_floats": [_i],
-    "rcmvs_pack_conv2d_tile": [_p, _p, _i, _p],
-    "rcmvs_conv2d_tile_fwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p],
-    "rcmvs_conv2d_stem_weight_floats": [],
-    "rcmvs_pack_conv2d_stem": [_p, _p, _p],
-    "rcmvs_conv2d_stem_fwd": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
-    "rcmvs_conv1x1_fwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_conv1x1_mfma_fwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_fpn_out_fused": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_fpn_out_folded": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
-    "rcmvs_fpn_folded_mfma_floats": [],
-    "rcmvs_fpn_folded_mfma_pack": [_p, _p, _p],
-    "rcmvs_fpn_out_folded_mfma": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
-    "rcmvs_bn_stats": [_p, _p, _ll, _i, _p],
-    "rcmvs_bn_finalize": [_p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _i, _p],
-    "rcmvs_bn_bwd_finalize": [_p, _p, _p, _p, _p, _p, _i, _p],
-    "rcmvs_scale_shift_relu": [_p, _p, _p, _p, _p, _ll, _i, _i, _p],
-    "rcmvs_bn_norm_fwd": [_p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _ll, _i, _i, _p],
-    "rcmvs_bn_norm_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _ll, _i, _i, _p],
-    "rcmvs_bn_bwd_reduce": [_p, _p, _p, _p, _p, _p, _p, _ll, _i, _i, _p],
-    "rcmvs_bn_bwd_apply": [_p, _p, _p, _p, _p, _p, _p, _p, _ll, _i, _i, _p],
-    "rcmvs_conv3d_wgrad": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_wgrad_finish": [_p, _p, _i, _i, _i, _p],
-    "rcmvs_conv3d_dgrad_c1": [_p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "rcmvs_depth_head_bwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "rcmvs_warp_noref_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_packed_weight_floats": [_i, _i],
-    "rcmvs_pack_conv3d_weight": [_p, _p, _i, _i, _i, _p],
-    "rcmvs_pack_conv3d_weight_sel": [_p, _p, _i, _i, _i, _i, _p],
-    "rcmvs_conv3d_images": [_i, _i, _i, _i, _i],
-    "rcmvs_debug_conv3d_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_debug_deconv3d_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_conv3d_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_deconv3d_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_rgb_to_nhwc4": [_p, _p, _i, _i, _i, _p],
-    "rcmvs_pack_conv2d_weight": [_p, _p, _i, _i, _i, _i, _p],
-    "rcmvs_conv2d_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_depth_head_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "rcmvs_depth_head_scaled_fwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "rcmvs_resize_planes_fwd": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_gu_sample_fwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "rcmvs_point_feats_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "rcmvs_nerf_mlp_fwd": [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p],
-    "rcmvs_nerf_mlp_embedded_fwd": [_p, _i, _p, _p, _p, _p, _ll, _p],
-    "rcmvs_nerf_mlp_train_fwd": [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p],
-    "rcmvs_nerf_mlp_bwd": [_p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _p],
-    "rcmvs_nerf_train_workspace_floats": [_ll],
-    "rcmvs_nerf_bwd_workspace_floats": [_ll],
-    "rcmvs_nerf_weight_floats": [],
-    "rcmvs_nerf_workspace_floats": [_ll],
-    "rcmvs_pack_nerf_weights": [_p, _p, _p],
-    "rcmvs_composite_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _p],
-    # DTU point-cloud scorer (additive entry points of version 106)
-    "rcmvs_pc_bbox": [_p, _ll, _p, _p, _p],
-    "rcmvs_pc_grid_build": [_p, _ll, _p, _p, _p, _p, _p, _p, _p, _p, _p],
-    "rcmvs_pc_nearest": [_p, _ll, _p, _p, _p, _p, _ll, _d, _p, _p, _p],
-    "rcmvs_pc_reduce_init": [_p, _p, _ll, _p, _p, _p, _p],
-    "rcmvs_pc_reduce_round": [_p, _p, _p, _p, _p, _p, _p, _ll, _d, _p, _p],
-    "rcmvs_pc_reduce_finish": [_p, _p, _ll, _p, _p],
-    "rcmvs_pc_select": [_p, _p, _ll, _i, _p, _p, _i, _i, _i, _d, _p, _p, _p, _p],
-    "rcmvs_pc_moments": [_p, _p, _p, _p, _p],
-    "rcmvs_pc_mesh_rows": [_p, _ll, _p, _ll, _d, _p, _p, _p],
-    "rcmvs_pc_mesh_count": [_p, _ll, _p, _ll, _d, _p, _ll, _p, _p, _p, _p, _p],
-    "rcmvs_pc_mesh_emit": [_p, _ll, _p, _ll, _d, _p, _p, _ll, _ll, _p, _p, _p, _p],
-    # training loader: image preparation (additive entry points of version 106)
-    "rcmvs_train_image_stats": [_p, _i, _i, _i, _p, _p, _p, _p],
-    "rcmvs_train_image_apply": [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
-    # validation: ground-truth depth metrics of one item (additive entry points of version 106)
-    "rcmvs_depth_metrics_workspace_bytes": [_ll, _ll, _ll],
-    "rcmvs_depth_metrics": [_p, _p, _p, _ll, _p, _p, _p, _ll, _p, _p, _p, _ll, _p, _p, _i, _p, _p, _p, _p],
-    "rcmvs_depth_metrics_timed": [_p, _p, _p, _ll, _p, _p, _p, _ll, _p, _p, _p, _ll, _p, _p, _i, _p, _p, _p, _p, _p, _p],
-    # depth colour map of the Tanks-and-Temples evaluation (additive entry points of version 106)
-    "rcmvs_depth_colormap_workspace_bytes": [],
-    "rcmvs_depth_colormap": [_p, _i, _i, _d, _p, _p, _p, _p, _p],
-}
-_RESTYPES = {"rcmvs_last_error_string": ctypes.c_char_p, "rcmvs_nerf_weight_floats": _ll, "rcmvs_nerf_workspace_floats": _ll, "rcmvs_nerf_train_workspace_floats": _ll, "rcmvs_nerf_bwd_workspace_floats": _ll,
-             "rcmvs_packed_weight_floats": _ll, "rcmvs_fpn_folded_mfma_floats": _ll, "rcmvs_conv2d_pair_weight_floats": _ll, "rcmvs_conv2d_stem_weight_floats": _ll, "rcmvs_conv2d_tile_weight_floats": _ll,
-             "rcmvs_depth_metrics_workspace_bytes": _ll, "rcmvs_depth_colormap_workspace_bytes": _ll}
 
 _lib = None
 
 
 class RcmvsError(RuntimeError):
     pass
+
+
+# The header is the binding's only table: every `<ret> rcmvs_name(<params>);` it declares becomes a row of SIGNATURES, every
+# `#define RCMVS_<NAME> <integer>` an entry of CONSTANTS.  The C types of the ABI are a closed set; anything else is an error, never a guess.
+_CTYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong}
+
+
+def _const_expr(text):
+    """Value of a #define's expression: integer literals, <<, parentheses -- nothing else."""
+    def ev(node):
+        if isinstance(node, ast.Constant) and type(node.value) is int:
+            return node.value
+        if isinstance(node, ast.BinOp) and isinstance(node.op, ast.LShift):
+            return ev(node.left) << ev(node.right)
+        raise ValueError(text)
+    return ev(ast.parse(text.strip(), mode="eval").body)
+
+
+def _ctype(decl, what, c_type):
+    if c_type not in _CTYPES:
+        raise RcmvsError(f"{HEADER}: `{decl}`: {what} type `{c_type}` is outside the ABI's types ({', '.join(_CTYPES)}, pointers)")
+    return _CTYPES[c_type]
+
+
+def parse_header(text):
+    """The text of include/rcmvs.h -> (SIGNATURES name -> argtypes, _RESTYPES name -> restype where it is not int, CONSTANTS)."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    signatures, restypes, constants, code = {}, {}, {}, []
+    for line in text.splitlines():
+        if not line.lstrip().startswith("#"):
+            code.append(line)
+            continue
+        m = re.match(r"\s*#\s*define\s+(RCMVS_\w+)\s+(\S.*)", line)          # a macro without a value (the include guard) is no constant
+        if m:
+            try:
+                value = _const_expr(m.group(2))
+            except (ValueError, SyntaxError):
+                raise RcmvsError(f"{HEADER}: `{line.strip()}`: not an integer expression of literals, << and parentheses") from None
+            if m.group(1) in constants:
+                raise RcmvsError(f"{HEADER}: {m.group(1)} is defined twice")
+            constants[m.group(1)] = value
+    for decl in re.sub(r'extern\s+"C"\s*\{', " ", "\n".join(code)).split(";"):
+        decl = " ".join(decl.split())
+        if "rcmvs_" not in decl:
+            continue
+        m = re.fullmatch(r"([\w\s*]+?)\s*\b(rcmvs_\w+)\s*\(([^()]*)\)", decl)
+        if not m:
+            raise RcmvsError(f"{HEADER}: `{decl}` is not a complete `<type> rcmvs_name(<parameters>);` declaration")
+        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
+        if name in signatures:
+            raise RcmvsError(f"{HEADER}: {name} is declared twice")
+        if ret.replace("const", "").replace(" ", "") == "char*":
+            restypes[name] = ctypes.c_char_p
+        elif ret != "int":
+            restypes[name] = _ctype(decl, "return", ret)
+        argtypes = []
+        for param in ([] if params == "void" else params.split(",")):
+            if "*" in param:
+                argtypes.append(ctypes.c_void_p)
+                continue
+            words = [w for w in param.split() if w != "const"]
+            if len(words) < 2 or not words[-1].isidentifier():
+                raise RcmvsError(f"{HEADER}: `{decl}`: parameter `{param.strip()}` is not `<type> <name>`")
+            argtypes.append(_ctype(decl, "parameter", " ".join(words[:-1])))
+        signatures[name] = argtypes
+    return signatures, restypes, constants
+
+
+def _read_header():
+    try:
+        with open(HEADER) as f:
+            return f.read()
+    except FileNotFoundError:
+        raise RcmvsError(f"{HEADER} is missing: the ctypes binding is derived from the C header, which was expected there "
+                         "(include/rcmvs.h next to the rc_mvsnet_amd package)") from None
+
+
+# name -> argtypes (restype is int unless listed in _RESTYPES), and the header's integer macros
+SIGNATURES, _RESTYPES, CONSTANTS = parse_header(_read_header())
+REQUIRED_VERSION = CONSTANTS["RCMVS_VERSION"]      # the RCMVS_VERSION of the header this binding is derived from
 
 
 def sources():
@@ -200,3 +159,11 @@ def check(rc, what):
     if rc != 0:
         msg = load().rcmvs_last_error_string()
         raise RcmvsError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
+
+
+def call(name, *args):
+    """Call the status-returning entry point `name` (the full exported name, e.g. "rcmvs_conv3d_fwd") of the loaded library; a non-zero status
+    raises RcmvsError with the library's message.  The function is looked up on the current handle at every call."""
+    rc = getattr(_lib or load(), name)(*args)
+    if rc:
+        check(rc, name[len("rcmvs_"):])

@@ -70,9 +70,9 @@ def depth_colormap(depth, percentile=95.0, lut=MAGMA_R, return_stats=False):
     ws, table = _device_state(depth.device, lut)
     rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=depth.device)
     stats = torch.empty(4, dtype=torch.float32, device=depth.device)
-    _lib.check(_lib.load().rcmvs_depth_colormap(_chk(depth, "depth"), H, W, float(percentile), _chk(table, "lut", torch.uint8),
-                                                _chk(rgb, "rgb", torch.uint8), _chk(stats, "stats"), _chk(ws, "workspace", torch.uint8),
-                                                _stream()), "depth_colormap")
+    _lib.call("rcmvs_depth_colormap", _chk(depth, "depth"), H, W, float(percentile), _chk(table, "lut", torch.uint8),
+              _chk(rgb, "rgb", torch.uint8), _chk(stats, "stats"), _chk(ws, "workspace", torch.uint8),
+              _stream())
     return (rgb, stats[:2], stats) if return_stats else (rgb, stats[:2])
 
 

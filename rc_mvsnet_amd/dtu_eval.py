@@ -36,7 +36,7 @@ from . import _lib
 from .ops import _chk, _stream
 
 BLOCK, SCAN_TILE = 256, 2048                        # csrc/pointcloud.hip
-MAX_CELLS = 1 << 24                                 # RCMVS_PC_MAX_CELLS
+MAX_CELLS = _lib.CONSTANTS["RCMVS_PC_MAX_CELLS"]
 BBOX_BLOCKS, MOMENT_BLOCKS = 1024, 256
 LATTICE = 60.0                                      # MaxDistCP's block edge (PointCompareMain: MaxDist = 60)
 USED_SETS = (1, 4, 9, 10, 11, 12, 13, 15, 23, 24, 29, 32, 33, 34, 48, 49, 62, 75, 77, 110, 114, 118)     # GetUsedSets.m
@@ -79,7 +79,7 @@ def bbox(pts):
         raise _lib.RcmvsError("bbox: empty cloud")
     part = torch.empty(6 * BBOX_BLOCKS, device=pts.device, dtype=torch.float32)
     out = torch.empty(6, device=pts.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_pc_bbox(_chk(pts, "pts"), n, _chk(part, "part"), _chk(out, "out"), _stream()), "pc_bbox")
+    _lib.call("rcmvs_pc_bbox", _chk(pts, "pts"), n, _chk(part, "part"), _chk(out, "out"), _stream())
     o = out.cpu().numpy()
     return o[:3], o[3:]
 
@@ -120,10 +120,10 @@ class Grid:
         self.sorted_idx = torch.empty(n, device=dev, dtype=torch.int32)
         self._g = _dbl(self.origin + [self.h])
         self._d = (ctypes.c_int * 3)(*self.dims)
-        _lib.check(_lib.load().rcmvs_pc_grid_build(
+        _lib.call("rcmvs_pc_grid_build",
             _chk(pts, "pts"), n, _host_ptr(self._g), _host_ptr(self._d), _chk(key, "key", torch.int32), _chk(count, "count", torch.int32),
             _chk(scan_work, "scan_work", torch.int32), _chk(self.cell_start, "cell_start", torch.int32), _chk(self.sorted, "sorted"),
-            _chk(self.sorted_idx, "sorted_idx", torch.int32), _stream()), "pc_grid_build")
+            _chk(self.sorted_idx, "sorted_idx", torch.int32), _stream())
 
 
 def lattice_bounds(bb, edge=LATTICE):
@@ -154,9 +154,8 @@ def nearest_distances(q_from, q_to, cap=60.0, lattice=None):
         args = (_host_ptr(grid._g), _host_ptr(grid._d), _chk(grid.cell_start, "cell_start", torch.int32), _chk(grid.sorted, "sorted"))
     else:
         grid, args = None, (None, None, None, None)
-    _lib.check(_lib.load().rcmvs_pc_nearest(_chk(q_from, "q_from"), n_from, *args, n_to, float(cap),
-                                            None if lat is None else _host_ptr(lat), _chk(out, "out", torch.float64), _stream()),
-               "pc_nearest")
+    _lib.call("rcmvs_pc_nearest", _chk(q_from, "q_from"), n_from, *args, n_to, float(cap),
+              None if lat is None else _host_ptr(lat), _chk(out, "out", torch.float64), _stream())
     return out
 
 
@@ -181,20 +180,19 @@ def reduce_points(pts, dst=0.2, order=None, seed=0):
     if order.shape != (n,) or not torch.equal(torch.sort(order).values, torch.arange(n, device=dev)):
         raise _lib.RcmvsError("reduce_points: order must be a permutation of 0 .. n-1")
     grid = Grid(pts, h_min=dst * 1.01)            # every neighbour within dst lies in the 27 cells around a point
-    lib = _lib.load()
     rank = torch.empty(n, device=dev, dtype=torch.int32)
     sorted_rank = torch.empty(n, device=dev, dtype=torch.int32)
     state = [torch.empty(n, device=dev, dtype=torch.uint8) for _ in range(2)]
     undecided = torch.empty(1, device=dev, dtype=torch.int32)
-    _lib.check(lib.rcmvs_pc_reduce_init(_chk(order, "order", torch.int64), _chk(grid.sorted_idx, "sorted_idx", torch.int32), n,
-                                        _chk(rank, "rank", torch.int32), _chk(sorted_rank, "sorted_rank", torch.int32),
-                                        _chk(state[0], "state", torch.uint8), _stream()), "pc_reduce_init")
+    _lib.call("rcmvs_pc_reduce_init", _chk(order, "order", torch.int64), _chk(grid.sorted_idx, "sorted_idx", torch.int32), n,
+              _chk(rank, "rank", torch.int32), _chk(sorted_rank, "sorted_rank", torch.int32),
+              _chk(state[0], "state", torch.uint8), _stream())
     rounds = 0
     while True:
-        _lib.check(lib.rcmvs_pc_reduce_round(_host_ptr(grid._g), _host_ptr(grid._d), _chk(grid.cell_start, "cell_start", torch.int32),
-                                             _chk(grid.sorted, "sorted"), _chk(sorted_rank, "sorted_rank", torch.int32),
-                                             _chk(state[0], "s_in", torch.uint8), _chk(state[1], "s_out", torch.uint8), n, float(dst),
-                                             _chk(undecided, "undecided", torch.int32), _stream()), "pc_reduce_round")
+        _lib.call("rcmvs_pc_reduce_round", _host_ptr(grid._g), _host_ptr(grid._d), _chk(grid.cell_start, "cell_start", torch.int32),
+                  _chk(grid.sorted, "sorted"), _chk(sorted_rank, "sorted_rank", torch.int32),
+                  _chk(state[0], "s_in", torch.uint8), _chk(state[1], "s_out", torch.uint8), n, float(dst),
+                  _chk(undecided, "undecided", torch.int32), _stream())
         rounds += 1
         state.reverse()
         left = int(undecided.item())
@@ -204,8 +202,8 @@ def reduce_points(pts, dst=0.2, order=None, seed=0):
             raise _lib.RcmvsError(f"reduce_points: {left} points still undecided after {rounds} rounds")
     last_reduce_rounds = rounds
     kept = torch.empty(n, device=dev, dtype=torch.uint8)
-    _lib.check(lib.rcmvs_pc_reduce_finish(_chk(state[0], "state", torch.uint8), _chk(grid.sorted_idx, "sorted_idx", torch.int32), n,
-                                          _chk(kept, "kept", torch.uint8), _stream()), "pc_reduce_finish")
+    _lib.call("rcmvs_pc_reduce_finish", _chk(state[0], "state", torch.uint8), _chk(grid.sorted_idx, "sorted_idx", torch.int32), n,
+              _chk(kept, "kept", torch.uint8), _stream())
     from .fusion import compact_points
     reduced, _ = compact_points(kept, pts)
     return kept.bool(), reduced
@@ -253,16 +251,15 @@ def select_stats(pts, d, mode, params, thresh, obs_mask=None):
     work = torch.empty(2 * nblk + 1 + _cdiv(nblk, SCAN_TILE) + 1, device=dev, dtype=torch.int32)
     sel = torch.empty(n, device=dev, dtype=torch.float64)
     p = _dbl(prm)
-    lib = _lib.load()
-    _lib.check(lib.rcmvs_pc_select(_chk(pts, "pts"), _chk(d, "d", torch.float64), n, code, _host_ptr(p),
-                                   None if mask is None else _chk(mask, "obs_mask", torch.uint8), s1, s2, s3, float(thresh),
-                                   _chk(flags, "flags", torch.uint8), _chk(sel, "out", torch.float64), _chk(work, "work", torch.int32),
-                                   _stream()), "pc_select")
+    _lib.call("rcmvs_pc_select", _chk(pts, "pts"), _chk(d, "d", torch.float64), n, code, _host_ptr(p),
+              None if mask is None else _chk(mask, "obs_mask", torch.uint8), s1, s2, s3, float(thresh),
+              _chk(flags, "flags", torch.uint8), _chk(sel, "out", torch.float64), _chk(work, "work", torch.int32),
+              _stream())
     count = work[2 * nblk:2 * nblk + 1]
     part = torch.empty(MOMENT_BLOCKS, device=dev, dtype=torch.float64)
     stats = torch.empty(3, device=dev, dtype=torch.float64)
-    _lib.check(lib.rcmvs_pc_moments(_chk(sel, "x", torch.float64), _chk(count, "count", torch.int32), _chk(part, "part", torch.float64),
-                                    _chk(stats, "stats", torch.float64), _stream()), "pc_moments")
+    _lib.call("rcmvs_pc_moments", _chk(sel, "x", torch.float64), _chk(count, "count", torch.int32), _chk(part, "part", torch.float64),
+              _chk(stats, "stats", torch.float64), _stream())
     st = stats.cpu().tolist()
     k = int(st[0])
     sel = sel[:k]
@@ -314,12 +311,11 @@ def sample_mesh(verts, faces, dst=0.2):
             raise _lib.RcmvsError(f"sample_mesh: face indices outside 0 .. {nv - 1}")
         faces = faces.to(torch.int32)
     faces = faces.contiguous()
-    dev, lib, dst = verts.device, _lib.load(), float(dst)
+    dev, dst = verts.device, float(dst)
     args = (_chk(verts, "verts"), nv, _chk(faces, "faces", torch.int32), m, dst)
     tri_rows = torch.empty(m, device=dev, dtype=torch.int32)
     totals = torch.empty(3, device=dev, dtype=torch.int64)
-    _lib.check(lib.rcmvs_pc_mesh_rows(*args, _chk(tri_rows, "tri_rows", torch.int32), _chk(totals, "totals", torch.int64), _stream()),
-               "pc_mesh_rows")
+    _lib.call("rcmvs_pc_mesh_rows", *args, _chk(tri_rows, "tri_rows", torch.int32), _chk(totals, "totals", torch.int64), _stream())
     rows, bad = totals[:2].tolist()
     if bad:
         raise _lib.RcmvsError(f"sample_mesh: {bad} faces index outside 0 .. {nv - 1}")
@@ -330,17 +326,17 @@ def sample_mesh(verts, faces, dst=0.2):
     scan_work = torch.empty(_cdiv(max(m, rows), SCAN_TILE) + 1, device=dev, dtype=torch.int32)
     tri_row_start = torch.empty(m + 1, device=dev, dtype=torch.int32)
     row_len = torch.empty(rows, device=dev, dtype=torch.int32)
-    _lib.check(lib.rcmvs_pc_mesh_count(*args, _chk(tri_rows, "tri_rows", torch.int32), rows, _chk(scan_work, "scan_work", torch.int32),
-                                       _chk(tri_row_start, "tri_row_start", torch.int32), _chk(row_len, "row_len", torch.int32),
-                                       _chk(totals, "totals", torch.int64), _stream()), "pc_mesh_count")
+    _lib.call("rcmvs_pc_mesh_count", *args, _chk(tri_rows, "tri_rows", torch.int32), rows, _chk(scan_work, "scan_work", torch.int32),
+              _chk(tri_row_start, "tri_row_start", torch.int32), _chk(row_len, "row_len", torch.int32),
+              _chk(totals, "totals", torch.int64), _stream())
     samples = int(totals[2])
     if nv + samples >= 1 << 31:
         raise _lib.RcmvsError(f"sample_mesh: {nv} vertices + {samples} samples (dst {dst}): the scorer takes below 2^31 points")
     row_start = torch.empty(rows + 1, device=dev, dtype=torch.int32)
     out = torch.empty((nv + samples, 3), device=dev, dtype=torch.float32)
-    _lib.check(lib.rcmvs_pc_mesh_emit(*args, _chk(tri_row_start, "tri_row_start", torch.int32), _chk(row_len, "row_len", torch.int32),
-                                      rows, samples, _chk(scan_work, "scan_work", torch.int32), _chk(row_start, "row_start", torch.int32),
-                                      _chk(out, "out"), _stream()), "pc_mesh_emit")
+    _lib.call("rcmvs_pc_mesh_emit", *args, _chk(tri_row_start, "tri_row_start", torch.int32), _chk(row_len, "row_len", torch.int32),
+              rows, samples, _chk(scan_work, "scan_work", torch.int32), _chk(row_start, "row_start", torch.int32),
+              _chk(out, "out"), _stream())
     return out
 
 

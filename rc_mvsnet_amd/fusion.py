@@ -19,7 +19,7 @@ from . import _lib, scan_io
 from .data_io import read_pfm
 from .ops import _chk, _stream
 
-MAX_SRC = 16      # RCMVS_FUSE_MAX_SRC
+MAX_SRC = _lib.CONSTANTS["RCMVS_FUSE_MAX_SRC"]
 REF_MATS, SRC_MATS = 30, 42
 
 
@@ -62,12 +62,12 @@ def fuse_view(depth_all, ref_idx, src_idx, conf, img, mats, prob_threshold, num_
     dbg_g = torch.empty((N, H, W), device=dev, dtype=torch.uint8) if debug else None
     dbg_xy = torch.empty((N, H, W, 2), device=dev, dtype=torch.float32) if debug else None
     idx = (ctypes.c_int * N)(*[int(i) for i in src_idx])
-    _lib.check(_lib.load().rcmvs_fuse_view(
+    _lib.call("rcmvs_fuse_view",
         _chk(depth_all, "depth_all"), int(ref_idx), ctypes.cast(idx, ctypes.c_void_p), _chk(conf, "conf"), _ptr(img, "img", torch.float32),
         _chk(mats, "mats", torch.float64), float(prob_threshold), int(num_consistent), float(img_dist_thresh), float(depth_thresh),
         _chk(masks, "masks", torch.uint8), _chk(depth_avg, "depth_avg"), _chk(xyz, "xyz"), _ptr(rgb, "rgb", torch.uint8),
         _ptr(dbg_d, "dbg_depth", torch.float32), _ptr(dbg_g, "dbg_geo", torch.uint8), _ptr(dbg_xy, "dbg_xy", torch.float32),
-        N, H, W, _stream()), "fuse_view")
+        N, H, W, _stream())
     out = {"masks": masks, "depth_avg": depth_avg, "xyz": xyz, "rgb": rgb}
     if debug:
         out.update({"depth_reprojected": dbg_d, "geo": dbg_g, "xy_src": dbg_xy})
@@ -81,9 +81,9 @@ def compact_points(mask, xyz, rgb=None):
     out_xyz = torch.empty((n, 3), device=dev, dtype=torch.float32)
     out_rgb = torch.empty((n, 3), device=dev, dtype=torch.uint8) if rgb is not None else None
     offsets = torch.empty((n + 255) // 256 + 1, device=dev, dtype=torch.int32)
-    _lib.check(_lib.load().rcmvs_compact_points(_chk(mask, "mask", torch.uint8), _chk(xyz, "xyz"), _ptr(rgb, "rgb", torch.uint8),
-                                                _chk(out_xyz, "out_xyz"), _ptr(out_rgb, "out_rgb", torch.uint8),
-                                                _chk(offsets, "offsets", torch.int32), n, _stream()), "compact_points")
+    _lib.call("rcmvs_compact_points", _chk(mask, "mask", torch.uint8), _chk(xyz, "xyz"), _ptr(rgb, "rgb", torch.uint8),
+              _chk(out_xyz, "out_xyz"), _ptr(out_rgb, "out_rgb", torch.uint8),
+              _chk(offsets, "offsets", torch.int32), n, _stream())
     kept = int(offsets[-1])                                     # the one host synchronisation of a reference view
     return out_xyz[:kept], (out_rgb[:kept] if rgb is not None else None)
 

@@ -20,7 +20,7 @@ import torch.nn as nn
 from . import _lib
 from .ops import _chk, _stream
 
-MAX_VIEWS = 8     # RCMVS_UNSUP_MAX_VIEWS
+MAX_VIEWS = _lib.CONSTANTS["RCMVS_UNSUP_MAX_VIEWS"]
 
 
 # ---------------------------------------------------------------------------------------------------------- geometry
@@ -73,8 +73,8 @@ def inverse_warping(img, left_cam, right_cam, depth):
     img, depth = img.contiguous(), depth.detach().contiguous()
     warped = torch.empty_like(img)
     mask = torch.empty((B, H, W), device=img.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_inverse_warp(_chk(img, "img"), _chk(depth, "depth"), _chk(coef, "coef"), _chk(warped, "warped"),
-                                              _chk(mask, "mask"), B, H, W, _stream()), "inverse_warp")
+    _lib.call("rcmvs_inverse_warp", _chk(img, "img"), _chk(depth, "depth"), _chk(coef, "coef"), _chk(warped, "warped"),
+              _chk(mask, "mask"), B, H, W, _stream())
     return warped, mask.unsqueeze(-1)
 
 
@@ -94,10 +94,10 @@ class UnsupStageLossFn(torch.autograd.Function):
         sums = torch.empty(4 * Vs + 2, device=dev, dtype=torch.float64)
         counts = torch.empty(Vs, device=dev, dtype=torch.int32)
         out = torch.empty(4 + Vs, device=dev, dtype=torch.float32)
-        _lib.check(_lib.load().rcmvs_unsup_loss_fwd(
+        _lib.call("rcmvs_unsup_loss_fwd",
             _chk(ref, "ref"), _chk(srcs, "srcs"), _chk(depth, "depth"), _chk(coef, "coef"), _chk(warped, "warped"),
             _chk(masks, "masks"), _chk(sums, "sums", torch.float64), _chk(counts, "counts", torch.int32), _chk(out, "out"),
-            B, Vs, H, W, _stream()), "unsup_loss_fwd")
+            B, Vs, H, W, _stream())
         ctx.save_for_backward(depth, ref, srcs, coef, warped, masks, counts)
         ctx.view_losses = out[4:]
         return out[:3].clone()
@@ -113,10 +113,10 @@ class UnsupStageLossFn(torch.autograd.Function):
         ws = torch.empty((B, H - 2, W - 2, 9), device=dev, dtype=torch.float32)
         kbuf = torch.empty(4 * Vs + 2, device=dev, dtype=torch.float32)
         gdepth = torch.empty_like(depth)
-        _lib.check(_lib.load().rcmvs_unsup_loss_bwd(
+        _lib.call("rcmvs_unsup_loss_bwd",
             _chk(ref, "ref"), _chk(srcs, "srcs"), _chk(depth, "depth"), _chk(coef, "coef"), _chk(warped, "warped"),
             _chk(masks, "masks"), _chk(counts, "counts", torch.int32), _chk(gout, "gout"), _chk(ws, "ws"), _chk(kbuf, "kbuf"),
-            _chk(gdepth, "gdepth"), B, Vs, H, W, _stream()), "unsup_loss_bwd")
+            _chk(gdepth, "gdepth"), B, Vs, H, W, _stream())
         return gdepth, None, None, None
 
 
@@ -166,8 +166,8 @@ class MaskedSmoothL1Fn(torch.autograd.Function):
     def forward(ctx, pred, target, mask):
         pred, target, mask = pred.contiguous(), target.contiguous(), mask.contiguous()
         sums = torch.empty(2, device=pred.device, dtype=torch.float64)
-        _lib.check(_lib.load().rcmvs_masked_sl1_fwd(_chk(pred, "pred"), _chk(target, "target"), _chk(mask, "mask"),
-                                                    _chk(sums, "sums", torch.float64), pred.numel(), _stream()), "masked_sl1_fwd")
+        _lib.call("rcmvs_masked_sl1_fwd", _chk(pred, "pred"), _chk(target, "target"), _chk(mask, "mask"),
+                  _chk(sums, "sums", torch.float64), pred.numel(), _stream())
         ctx.save_for_backward(pred, target, mask, sums)
         return (sums[0] / sums[1]).float()
 
@@ -176,9 +176,9 @@ class MaskedSmoothL1Fn(torch.autograd.Function):
         pred, target, mask, sums = ctx.saved_tensors
         g = g.reshape(1).contiguous().float()
         gp = torch.empty_like(pred)
-        _lib.check(_lib.load().rcmvs_masked_sl1_bwd(_chk(pred, "pred"), _chk(target, "target"), _chk(mask, "mask"),
-                                                    _chk(sums, "sums", torch.float64), _chk(g, "g"), _chk(gp, "grad"),
-                                                    pred.numel(), _stream()), "masked_sl1_bwd")
+        _lib.call("rcmvs_masked_sl1_bwd", _chk(pred, "pred"), _chk(target, "target"), _chk(mask, "mask"),
+                  _chk(sums, "sums", torch.float64), _chk(g, "g"), _chk(gp, "grad"),
+                  pred.numel(), _stream())
         return gp, None, None
 
 

@@ -56,9 +56,8 @@ def prepare_image(img_u8, out_hw, device, mean=MEAN, std=STD):
     src = torch.from_numpy(np.ascontiguousarray(img_u8)).to(device, non_blocking=True)
     out = torch.empty((3, h, w), device=device, dtype=torch.float32)
     mean, std = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-    _lib.check(_lib.load().rcmvs_prepare_image(_chk(src, "src", torch.uint8), _chk(out, "out"), H, W, h, w,
-                                               ctypes.cast(mean, ctypes.c_void_p), ctypes.cast(std, ctypes.c_void_p), _stream()),
-               "prepare_image")
+    _lib.call("rcmvs_prepare_image", _chk(src, "src", torch.uint8), _chk(out, "out"), H, W, h, w,
+              ctypes.cast(mean, ctypes.c_void_p), ctypes.cast(std, ctypes.c_void_p), _stream())
     return out
 
 
@@ -309,7 +308,6 @@ def prepare_train_images(raw_u8, aug, device, return_u8=False):
     if not (np.isfinite(gamma).all() and (gamma > 0).all()):
         raise _lib.RcmvsError(f"prepare_train_images: gamma must be finite and > 0, got {gamma}")
     params = np.ascontiguousarray(np.concatenate([factors.view(np.int32), order], axis=1))            # (V,8) words: ta::ViewParams
-    lib = _lib.load()
     src = torch.from_numpy(np.ascontiguousarray(raw_u8)).to(device, non_blocking=True)
     params_dev = torch.from_numpy(params).to(device, non_blocking=True)
     lut_seg = tone_table().to(device, non_blocking=True)
@@ -318,13 +316,12 @@ def prepare_train_images(raw_u8, aug, device, return_u8=False):
     out = {k: torch.empty((V, 3, H, W), device=device, dtype=torch.float32) for k in ("imgs", "center_imgs", "imgs_aug")}
     u8 = torch.empty((V, H, W, 3), device=device, dtype=torch.uint8) if return_u8 else None
     host = ctypes.c_void_p(params.ctypes.data)
-    _lib.check(lib.rcmvs_train_image_stats(_chk(src, "src", torch.uint8), V, H, W, host, _chk(params_dev, "params", torch.int32),
-                                           _chk(sums, "sums", torch.int64), _stream()), "train_image_stats")
-    _lib.check(lib.rcmvs_train_image_apply(_chk(src, "src", torch.uint8), V, H, W, host, _chk(params_dev, "params", torch.int32),
-                                           _chk(sums, "sums", torch.int64), _chk(lut_seg, "lut_seg"), _chk(lut_aug, "lut_aug"),
-                                           _chk(out["imgs"], "imgs"), _chk(out["center_imgs"], "center_imgs"), _chk(out["imgs_aug"], "imgs_aug"),
-                                           ctypes.c_void_p(0) if u8 is None else _chk(u8, "u8_out", torch.uint8), _stream()),
-               "train_image_apply")
+    _lib.call("rcmvs_train_image_stats", _chk(src, "src", torch.uint8), V, H, W, host, _chk(params_dev, "params", torch.int32),
+              _chk(sums, "sums", torch.int64), _stream())
+    _lib.call("rcmvs_train_image_apply", _chk(src, "src", torch.uint8), V, H, W, host, _chk(params_dev, "params", torch.int32),
+              _chk(sums, "sums", torch.int64), _chk(lut_seg, "lut_seg"), _chk(lut_aug, "lut_aug"),
+              _chk(out["imgs"], "imgs"), _chk(out["center_imgs"], "center_imgs"), _chk(out["imgs_aug"], "imgs_aug"),
+              ctypes.c_void_p(0) if u8 is None else _chk(u8, "u8_out", torch.uint8), _stream())
     if return_u8:
         out["jitter_u8"] = u8
     out["sums"] = sums
@@ -592,10 +589,9 @@ class DTUValDataset(torch.utils.data.Dataset):
         V, H, W = src.shape[:3]
         imgs = torch.empty((V, 3, H, W), device=self.device, dtype=torch.float32)
         zero, one = (ctypes.c_float * 3)(0.0, 0.0, 0.0), (ctypes.c_float * 3)(1.0, 1.0, 1.0)
-        lib = _lib.load()
         for v in range(V):
-            _lib.check(lib.rcmvs_prepare_image(_chk(src[v], "src", torch.uint8), _chk(imgs[v], "imgs"), H, W, H, W,
-                                               ctypes.cast(zero, ctypes.c_void_p), ctypes.cast(one, ctypes.c_void_p), _stream()), "prepare_image")
+            _lib.call("rcmvs_prepare_image", _chk(src[v], "src", torch.uint8), _chk(imgs[v], "imgs"), H, W, H, W,
+                      ctypes.cast(zero, ctypes.c_void_p), ctypes.cast(one, ctypes.c_void_p), _stream())
         item["imgs"] = imgs
         f32 = host["f32"].to(self.device, non_blocking=True)
         at = 0

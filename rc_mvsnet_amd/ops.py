@@ -15,8 +15,8 @@ from . import _lib
 # bench.py sets this to a list to have every K1 launch bracketed by HIP events recorded on the
 # launch stream (torch's current stream); None = no instrumentation.
 K1_EVENTS = None
-K1_UNIFORM_PLANES = 1          # RCMVS_K1_UNIFORM_PLANES (include/rcmvs.h)
-K1_FAST_BLEND = 2              # RCMVS_K1_FAST_BLEND: the FMA-contracted forms (<= 2e-6 of the value range from the exact kernel)
+K1_UNIFORM_PLANES = _lib.CONSTANTS["RCMVS_K1_UNIFORM_PLANES"]
+K1_FAST_BLEND = _lib.CONSTANTS["RCMVS_K1_FAST_BLEND"]      # the FMA-contracted forms (<= 2e-6 of the value range from the exact kernel)
 # same for the 3-D convolutions: list of (event0, event1, key) with key = (kind, B, D, H, W, Ci, Co), kind 's1' | 's2' | 't2'
 CONV_EVENTS = None
 
@@ -66,7 +66,7 @@ def to_channels_last(x):
     N, C = x.shape[:2]
     S = x[0, 0].numel()
     out = torch.empty((N, *x.shape[2:], C), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_nchw_to_nhwc(_chk(x, "x"), _chk(out, "out"), N, C, S, _stream()), "nchw_to_nhwc")
+    _lib.call("rcmvs_nchw_to_nhwc", _chk(x, "x"), _chk(out, "out"), N, C, S, _stream())
     return out
 
 
@@ -75,7 +75,7 @@ def to_channels_first(x):
     N, C = x.shape[0], x.shape[-1]
     S = x[0, ..., 0].numel()
     out = torch.empty((N, C, *x.shape[1:-1]), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_nhwc_to_nchw(_chk(x, "x"), _chk(out, "out"), N, C, S, _stream()), "nhwc_to_nchw")
+    _lib.call("rcmvs_nhwc_to_nchw", _chk(x, "x"), _chk(out, "out"), N, C, S, _stream())
     return out
 
 
@@ -85,8 +85,7 @@ def compose_homography(proj):
     B, V = proj.shape[:2]
     rot = torch.empty((B, V - 1, 9), device=proj.device, dtype=torch.float32)
     trans = torch.empty((B, V - 1, 3), device=proj.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_compose_homography(_chk(proj, "proj"), _chk(rot, "rot"), _chk(trans, "trans"), B, V, _stream()),
-               "compose_homography")
+    _lib.call("rcmvs_compose_homography", _chk(proj, "proj"), _chk(rot, "rot"), _chk(trans, "trans"), B, V, _stream())
     return rot, trans
 
 
@@ -98,8 +97,8 @@ def compose_homography_stages(projs, zero=None):
     rot = torch.empty((n, B, V - 1, 9), device=projs[0].device, dtype=torch.float32)
     trans = torch.empty((n, B, V - 1, 3), device=projs[0].device, dtype=torch.float32)
     ptrs = [_chk(p, "proj") for p in projs] + [ctypes.c_void_p(0)] * (4 - n)
-    _lib.check(_lib.load().rcmvs_compose_homography_stages(ptrs[0], ptrs[1], ptrs[2], ptrs[3], n, _chk(rot, "rot"), _chk(trans, "trans"), B, V,
-                                                           _opt(zero, "zero"), 0 if zero is None else zero.numel(), _stream()), "compose_homography_stages")
+    _lib.call("rcmvs_compose_homography_stages", ptrs[0], ptrs[1], ptrs[2], ptrs[3], n, _chk(rot, "rot"), _chk(trans, "trans"), B, V,
+              _opt(zero, "zero"), 0 if zero is None else zero.numel(), _stream())
     return rot, trans
 
 
@@ -109,21 +108,21 @@ def hypothesis_planes(prev_depth, depth_values, full_hw, scale, ndepth, ratio):
     H, W = full_hw
     planes = torch.empty((B, H // scale, W // scale, 2), device=depth_values.device, dtype=torch.float32)
     hp, wp = (prev_depth.shape[-2:] if prev_depth is not None else (0, 0))
-    _lib.check(_lib.load().rcmvs_hypothesis_planes(_opt(prev_depth, "prev_depth"), _chk(depth_values, "depth_values"),
-                                                   _chk(planes, "planes"), B, hp, wp, H, W, scale, ndepth, float(ratio), ND,
-                                                   _stream()), "hypothesis_planes")
+    _lib.call("rcmvs_hypothesis_planes", _opt(prev_depth, "prev_depth"), _chk(depth_values, "depth_values"),
+              _chk(planes, "planes"), B, hp, wp, H, W, scale, ndepth, float(ratio), ND,
+              _stream())
     return planes
 
 
 # ------------------------------------------------------------------------------- K1
-ABSMAX_FLOATS = 1024      # RCMVS_ABSMAX_FLOATS of include/rcmvs.h: a bound is 64 slots, 16 floats apart
+ABSMAX_FLOATS = _lib.CONSTANTS["RCMVS_ABSMAX_FLOATS"]      # a bound is 64 slots, 16 floats apart
 
 
 def absmax(x, square=False, out=None):
     """Bound of max|x| (or its square) in the slot format conv3d(x_absmax=) takes: a (1024,) float vector whose maximum is the bound."""
     if out is None:
         out = torch.zeros(ABSMAX_FLOATS, device=x.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_absmax_fwd(_chk(x, "x"), x.numel(), int(bool(square)), _chk(out, "absmax"), _stream()), "absmax_fwd")
+    _lib.call("rcmvs_absmax_fwd", _chk(x, "x"), x.numel(), int(bool(square)), _chk(out, "absmax"), _stream())
     return out
 
 
@@ -135,10 +134,9 @@ def warp_variance(feats, rot, trans, planes, ndepth, variant=None, uniform_plane
     5 / 6 window form, 7 plane-pipelined gather form)."""
     B, V, h, w, C = feats.shape
     var = torch.empty((B, ndepth, h, w, C), device=feats.device, dtype=torch.float32)
+    args = (_chk(feats, "feats"), _chk(rot, "rot"), _chk(trans, "trans"), _chk(planes, "planes"), _chk(var, "var"), B, V, C, ndepth, h, w)
     if variant is not None:
-        _lib.check(_lib.load().rcmvs_debug_warp_variance_fwd(_chk(feats, "feats"), _chk(rot, "rot"), _chk(trans, "trans"),
-                                                             _chk(planes, "planes"), _chk(var, "var"), B, V, C, ndepth, h, w, int(variant),
-                                                             _stream()), "debug_warp_variance_fwd")
+        _lib.call("rcmvs_debug_warp_variance_fwd", *args, int(variant), _stream())
         return var
     hint = K1_FAST_BLEND | (K1_UNIFORM_PLANES if uniform_planes else 0)
     if K1_EVENTS is not None:
@@ -148,15 +146,10 @@ def warp_variance(feats, rot, trans, planes, ndepth, variant=None, uniform_plane
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
         ev[1].record()
-        _lib.check(_lib.load().rcmvs_warp_variance_timed_fwd(_chk(feats, "feats"), _chk(rot, "rot"), _chk(trans, "trans"),
-                                                             _chk(planes, "planes"), _chk(var, "var"), B, V, C, ndepth, h, w, hint,
-                                                             ctypes.c_void_p(ev[0].cuda_event), ctypes.c_void_p(ev[1].cuda_event), _stream()),
-                   "warp_variance_timed_fwd")
+        _lib.call("rcmvs_warp_variance_timed_fwd", *args, hint, ctypes.c_void_p(ev[0].cuda_event), ctypes.c_void_p(ev[1].cuda_event), _stream())
         K1_EVENTS.append(ev)
         return var
-    _lib.check(_lib.load().rcmvs_warp_variance_hint_fwd(_chk(feats, "feats"), _chk(rot, "rot"), _chk(trans, "trans"),
-                                                        _chk(planes, "planes"), _chk(var, "var"), B, V, C, ndepth, h, w, hint, _stream()),
-               "warp_variance_hint_fwd")
+    _lib.call("rcmvs_warp_variance_hint_fwd", *args, hint, _stream())
     return var
 
 
@@ -165,9 +158,9 @@ def warp_variance_win(feats, rot, trans, planes, ndepth, variant=5):
     B, V, h, w, C = feats.shape
     var = torch.empty((B, ndepth, h, w, C), device=feats.device, dtype=torch.float32)
     stats = torch.zeros(2, device=feats.device, dtype=torch.int32)
-    _lib.check(_lib.load().rcmvs_debug_warp_variance_win_fwd(_chk(feats, "feats"), _chk(rot, "rot"), _chk(trans, "trans"),
-                                                                 _chk(planes, "planes"), _chk(var, "var"), B, V, C, ndepth, h, w, int(variant),
-                                                                 _chk(stats, "stats", torch.int32), _stream()), "debug_warp_variance_win_fwd")
+    _lib.call("rcmvs_debug_warp_variance_win_fwd", _chk(feats, "feats"), _chk(rot, "rot"), _chk(trans, "trans"),
+              _chk(planes, "planes"), _chk(var, "var"), B, V, C, ndepth, h, w, int(variant),
+              _chk(stats, "stats", torch.int32), _stream())
     n = stats.cpu()
     return var, int(n[0]), int(n[1])
 
@@ -176,9 +169,9 @@ def warp_noref(feats, imgs, rot, trans, planes, ndepth, square_first):
     """feats (B,V,h,w,C), imgs (B,V,h,w,3) -> (B, 3(V-1)+C, D, h, w) in the reference's NCDHW."""
     B, V, h, w, C = feats.shape
     out = torch.empty((B, 3 * (V - 1) + C, ndepth, h, w), device=feats.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_warp_noref_fwd(_chk(feats, "feats"), _chk(imgs, "imgs"), _chk(rot, "rot"), _chk(trans, "trans"),
-                                                _chk(planes, "planes"), _chk(out, "out"), B, V, C, ndepth, h, w,
-                                                int(bool(square_first)), _stream()), "warp_noref_fwd")
+    _lib.call("rcmvs_warp_noref_fwd", _chk(feats, "feats"), _chk(imgs, "imgs"), _chk(rot, "rot"), _chk(trans, "trans"),
+              _chk(planes, "planes"), _chk(out, "out"), B, V, C, ndepth, h, w,
+              int(bool(square_first)), _stream())
     return out
 
 
@@ -190,16 +183,12 @@ def warp_variance_bwd(feats, rot, trans, planes, grad_var, grad_noref=None, vari
     if tuple(grad_var.shape) != (B, D, h, w, C) or (grad_noref is not None and grad_noref.shape != grad_var.shape):
         raise _lib.RcmvsError(f"warp_variance_bwd: gradient shape {tuple(grad_var.shape)} does not match (B,D,h,w,C)")
     gf = torch.zeros_like(feats)
+    args = (_chk(feats, "feats"), _chk(rot, "rot"), _chk(trans, "trans"), _chk(planes, "planes"), _chk(grad_var, "grad_var"),
+            _opt(grad_noref, "grad_noref"), _chk(gf, "grad_feats"), B, V, C, D, h, w)
     if variant:          # ablation twin (bit 0: no scatter -- timing only; bit 1: no run-length merging)
-        _lib.check(_lib.load().rcmvs_debug_warp_variance_bwd(_chk(feats, "feats"), _chk(rot, "rot"), _chk(trans, "trans"),
-                                                             _chk(planes, "planes"), _chk(grad_var, "grad_var"),
-                                                             _opt(grad_noref, "grad_noref"), _chk(gf, "grad_feats"),
-                                                             B, V, C, D, h, w, int(variant), _stream()), "debug_warp_variance_bwd")
-        return gf
-    _lib.check(_lib.load().rcmvs_warp_variance_bwd(_chk(feats, "feats"), _chk(rot, "rot"), _chk(trans, "trans"),
-                                                   _chk(planes, "planes"), _chk(grad_var, "grad_var"),
-                                                   _opt(grad_noref, "grad_noref"), _chk(gf, "grad_feats"),
-                                                   B, V, C, D, h, w, _stream()), "warp_variance_bwd")
+        _lib.call("rcmvs_debug_warp_variance_bwd", *args, int(variant), _stream())
+    else:
+        _lib.call("rcmvs_warp_variance_bwd", *args, _stream())
     return gf
 
 
@@ -263,6 +252,17 @@ def force_direct_conv(on):
     _CONV_IMPL = int(on)
 
 
+def _conv_event_start():
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    ev[0].record()
+    return ev
+
+
+def _conv_event_stop(ev, *key):
+    ev[1].record()
+    CONV_EVENTS.append(ev + (key,))      # only complete pairs are listed
+
+
 def conv3d_images(ci, co, stride=1, transposed=False, planar=False):
     """Mask of the blob image the production dispatch reads for this layer (rcmvs_conv3d_images)."""
     return int(_lib.load().rcmvs_conv3d_images(co, ci, int(stride), int(bool(transposed)), int(bool(planar))))
@@ -281,8 +281,7 @@ def pack_conv3d_weight(w, transposed=False, use=None):
     images = IMG_ALL
     if use is not None and not _CONV_IMPL:
         images = conv3d_images(Ci, Co, stride=use[0], transposed=(int(transposed) == 1), planar=use[1])
-    _lib.check(_lib.load().rcmvs_pack_conv3d_weight_sel(_chk(w, "w"), _chk(blob, "packed"), Co, Ci, int(transposed), images, _stream()),
-               "pack_conv3d_weight")
+    _lib.call("rcmvs_pack_conv3d_weight_sel", _chk(w, "w"), _chk(blob, "packed"), Co, Ci, int(transposed), images, _stream())
     return PackedWeight(blob, Ci, Co, int(transposed), images)
 
 
@@ -309,26 +308,19 @@ def conv3d(x, w_packed, scale=None, shift=None, residual=None, stride=1, relu=Fa
                     dtype=torch.float32)
     if residual is not None and residual.shape != y.shape:
         raise _lib.RcmvsError(f"conv3d: residual {tuple(residual.shape)} != output {tuple(y.shape)}")
-    ev = None
-    if CONV_EVENTS is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
+    ev = _conv_event_start() if CONV_EVENTS is not None else None
+    # the three entry points take the same arguments, the scaled one with a bound after x and after y; the last two with a kernel selector
     if x_absmax is not None or y_absmax is not None:
-        _lib.check(_lib.load().rcmvs_conv3d_scaled_fwd(_chk(x, "x"), _opt(x_absmax, "x_absmax"), _chk(w_packed.blob, "w"), _opt(scale, "scale"),
-                                                       _opt(shift, "shift"), _opt(residual, "residual"), _chk(y, "y"), _opt(y_absmax, "y_absmax"),
-                                                       B, D, H, W, Ci, Co, stride, int(relu), _CONV_IMPL | ((1 << 24) if y_absmax_square else 0), _stream()),
-                   "conv3d_scaled_fwd")
+        name, xb, yb = "rcmvs_conv3d_scaled_fwd", (_opt(x_absmax, "x_absmax"),), (_opt(y_absmax, "y_absmax"),)
+        impl = (_CONV_IMPL | ((1 << 24) if y_absmax_square else 0),)
     elif _CONV_IMPL:
-        _lib.check(_lib.load().rcmvs_debug_conv3d_fwd(_chk(x, "x"), _chk(w_packed.blob, "w"), _opt(scale, "scale"), _opt(shift, "shift"),
-                                                      _opt(residual, "residual"), _chk(y, "y"), B, D, H, W, Ci, Co, stride, int(relu),
-                                                      _CONV_IMPL, _stream()), "debug_conv3d_fwd")
+        name, xb, yb, impl = "rcmvs_debug_conv3d_fwd", (), (), (_CONV_IMPL,)
     else:
-        _lib.check(_lib.load().rcmvs_conv3d_fwd(_chk(x, "x"), _chk(w_packed.blob, "w"), _opt(scale, "scale"), _opt(shift, "shift"),
-                                                _opt(residual, "residual"), _chk(y, "y"), B, D, H, W, Ci, Co, stride, int(relu),
-                                                _stream()), "conv3d_fwd")
+        name, xb, yb, impl = "rcmvs_conv3d_fwd", (), (), ()
+    _lib.call(name, _chk(x, "x"), *xb, _chk(w_packed.blob, "w"), _opt(scale, "scale"), _opt(shift, "shift"), _opt(residual, "residual"),
+              _chk(y, "y"), *yb, B, D, H, W, Ci, Co, stride, int(relu), *impl, _stream())
     if ev is not None:
-        ev[1].record()
-        CONV_EVENTS.append(ev + (("s1" if stride == 1 else "s2", B, D, H, W, Ci, Co),))      # only complete pairs are listed
+        _conv_event_stop(ev, "s1" if stride == 1 else "s2", B, D, H, W, Ci, Co)
     return y
 
 
@@ -345,25 +337,17 @@ def deconv3d(x, w_packed, scale=None, shift=None, residual=None, relu=False, x_a
     if residual is not None and residual.shape != y.shape:
         raise _lib.RcmvsError(f"deconv3d: residual {tuple(residual.shape)} != output {tuple(y.shape)} "
                               "(volume sizes must be divisible by 8, as in the reference)")
-    ev = None
-    if CONV_EVENTS is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-    if x_absmax is not None or y_absmax is not None:
-        _lib.check(_lib.load().rcmvs_deconv3d_scaled_fwd(_chk(x, "x"), _opt(x_absmax, "x_absmax"), _chk(w_packed.blob, "w"), _opt(scale, "scale"),
-                                                         _opt(shift, "shift"), _opt(residual, "residual"), _chk(y, "y"), _opt(y_absmax, "y_absmax"),
-                                                         B, D, H, W, Ci, Co, int(relu), _CONV_IMPL, _stream()), "deconv3d_scaled_fwd")
+    ev = _conv_event_start() if CONV_EVENTS is not None else None
+    if x_absmax is not None or y_absmax is not None:      # argument layout of the three entry points: see conv3d
+        name, xb, yb, impl = "rcmvs_deconv3d_scaled_fwd", (_opt(x_absmax, "x_absmax"),), (_opt(y_absmax, "y_absmax"),), (_CONV_IMPL,)
     elif _CONV_IMPL:
-        _lib.check(_lib.load().rcmvs_debug_deconv3d_fwd(_chk(x, "x"), _chk(w_packed.blob, "w"), _opt(scale, "scale"), _opt(shift, "shift"),
-                                                        _opt(residual, "residual"), _chk(y, "y"), B, D, H, W, Ci, Co, int(relu),
-                                                        _CONV_IMPL, _stream()), "debug_deconv3d_fwd")
+        name, xb, yb, impl = "rcmvs_debug_deconv3d_fwd", (), (), (_CONV_IMPL,)
     else:
-        _lib.check(_lib.load().rcmvs_deconv3d_fwd(_chk(x, "x"), _chk(w_packed.blob, "w"), _opt(scale, "scale"), _opt(shift, "shift"),
-                                                  _opt(residual, "residual"), _chk(y, "y"), B, D, H, W, Ci, Co, int(relu),
-                                                  _stream()), "deconv3d_fwd")
+        name, xb, yb, impl = "rcmvs_deconv3d_fwd", (), (), ()
+    _lib.call(name, _chk(x, "x"), *xb, _chk(w_packed.blob, "w"), _opt(scale, "scale"), _opt(shift, "shift"), _opt(residual, "residual"),
+              _chk(y, "y"), *yb, B, D, H, W, Ci, Co, int(relu), *impl, _stream())
     if ev is not None:
-        ev[1].record()
-        CONV_EVENTS.append(ev + (("t2", B, D, H, W, Ci, Co),))
+        _conv_event_stop(ev, "t2", B, D, H, W, Ci, Co)
     return y
 
 
@@ -375,8 +359,8 @@ def conv2d_s2d(x, w_packed, scale=None, shift=None, relu=False):
     if w_packed.ci != 4 * C:
         raise _lib.RcmvsError(f"conv2d_s2d: input has {C} channels, the packed weight expects {w_packed.ci} = 4 x C")
     y = torch.empty((N, H // 2, W // 2, Co), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_conv2d_s2d_fwd(_chk(x, "x"), _chk(w_packed.blob, "w"), _opt(scale, "scale"), _opt(shift, "shift"),
-                                                _chk(y, "y"), N, H, W, C, Co, int(relu), _stream()), "conv2d_s2d_fwd")
+    _lib.call("rcmvs_conv2d_s2d_fwd", _chk(x, "x"), _chk(w_packed.blob, "w"), _opt(scale, "scale"), _opt(shift, "shift"),
+              _chk(y, "y"), N, H, W, C, Co, int(relu), _stream())
     return y
 
 
@@ -387,8 +371,7 @@ def pack_conv2d_pair(wa, wb):
         raise _lib.RcmvsError("pack_conv2d_pair: built for two 16 -> 16 3x3 layers")
     lib = _lib.load()
     img = torch.empty(int(lib.rcmvs_conv2d_pair_weight_floats()), device=wa.device, dtype=torch.float32)
-    _lib.check(lib.rcmvs_pack_conv2d_pair(_chk(wa.detach().float().contiguous(), "wa"), _chk(wb.detach().float().contiguous(), "wb"), _chk(img, "image"), _stream()),
-               "pack_conv2d_pair")
+    _lib.call("rcmvs_pack_conv2d_pair", _chk(wa.detach().float().contiguous(), "wa"), _chk(wb.detach().float().contiguous(), "wb"), _chk(img, "image"), _stream())
     return img
 
 
@@ -396,8 +379,8 @@ def conv2d_pair(x, image, scale_a, shift_a, scale_b, shift_b):
     """x (N,H,W,16) -> relu(bn_b(conv_b(relu(bn_a(conv_a(x)))))) (N,H,W,16): two 3x3 Conv2d blocks in one launch, the map between them in LDS."""
     N, H, W, C = x.shape
     y = torch.empty_like(x)
-    _lib.check(_lib.load().rcmvs_conv2d_pair_fwd(_chk(x, "x"), _chk(image, "image"), _chk(scale_a, "scale_a"), _chk(shift_a, "shift_a"),
-                                                 _chk(scale_b, "scale_b"), _chk(shift_b, "shift_b"), _chk(y, "y"), N, H, W, C, _stream()), "conv2d_pair_fwd")
+    _lib.call("rcmvs_conv2d_pair_fwd", _chk(x, "x"), _chk(image, "image"), _chk(scale_a, "scale_a"), _chk(shift_a, "shift_a"),
+              _chk(scale_b, "scale_b"), _chk(shift_b, "shift_b"), _chk(y, "y"), N, H, W, C, _stream())
     return y
 
 
@@ -408,7 +391,7 @@ def resize_rgb_cl(x, hw):
         raise _lib.RcmvsError("resize_rgb_cl: expects RGB images (N,3,H,W)")
     h, w = int(hw[0]), int(hw[1])
     y = torch.empty((N, h, w, 3), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_resize_rgb_cl(_chk(x, "x"), _chk(y, "y"), N, H, W, h, w, _stream()), "resize_rgb_cl")
+    _lib.call("rcmvs_resize_rgb_cl", _chk(x, "x"), _chk(y, "y"), N, H, W, h, w, _stream())
     return y
 
 
@@ -416,7 +399,7 @@ def rgb_to_nhwc4(x):
     """(N,3,H,W) -> (N,H,W,4), zero 4th channel."""
     N, _, H, W = x.shape
     y = torch.empty((N, H, W, 4), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_rgb_to_nhwc4(_chk(x, "x"), _chk(y, "y"), N, H, W, _stream()), "rgb_to_nhwc4")
+    _lib.call("rcmvs_rgb_to_nhwc4", _chk(x, "x"), _chk(y, "y"), N, H, W, _stream())
     return y
 
 
@@ -426,7 +409,7 @@ def pack_conv2d_weight(w, pad_in_to=None):
     Co, Ci, K, _ = w.shape
     Cip = Ci if pad_in_to is None else pad_in_to
     blob = torch.empty((K * K * Cip * Co,), device=w.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_pack_conv2d_weight(_chk(w, "w"), _chk(blob, "packed"), Co, Ci, Cip, K, _stream()), "pack_conv2d_weight")
+    _lib.call("rcmvs_pack_conv2d_weight", _chk(w, "w"), _chk(blob, "packed"), Co, Ci, Cip, K, _stream())
     pw = PackedWeight(blob, Cip, Co)
     pw.k = K
     return pw
@@ -442,9 +425,8 @@ def conv2d(x, w_packed, scale=None, shift=None, up_add=None, stride=1, relu=Fals
     y = torch.empty((N, Ho, Wo, Co), device=x.device, dtype=torch.float32)
     if up_add is not None and tuple(up_add.shape) != (N, Ho // 2, Wo // 2, Co):
         raise _lib.RcmvsError(f"conv2d: up_add {tuple(up_add.shape)} does not match half of the output {tuple(y.shape)}")
-    _lib.check(_lib.load().rcmvs_conv2d_fwd(_chk(x, "x"), _chk(w_packed.blob, "w"), _opt(scale, "scale"), _opt(shift, "shift"),
-                                            _opt(up_add, "up_add"), _chk(y, "y"), N, H, W, Ci, Co, K, stride, int(relu), _stream()),
-               "conv2d_fwd")
+    _lib.call("rcmvs_conv2d_fwd", _chk(x, "x"), _chk(w_packed.blob, "w"), _opt(scale, "scale"), _opt(shift, "shift"),
+              _opt(up_add, "up_add"), _chk(y, "y"), N, H, W, Ci, Co, K, stride, int(relu), _stream())
     return y
 
 
@@ -459,9 +441,8 @@ def conv1x1(x, w_packed, scale=None, shift=None, up_add=None, relu=False, ysq_ab
     if up_add is not None and tuple(up_add.shape) != (N, H // 2, W // 2, Co):
         raise _lib.RcmvsError(f"conv1x1: up_add {tuple(up_add.shape)} does not match half of the output")
     y = torch.empty((N, H, W, Co), device=x.device, dtype=torch.float32)
-    fn = _lib.load().rcmvs_conv1x1_mfma_fwd if mfma else _lib.load().rcmvs_conv1x1_fwd
-    _lib.check(fn(_chk(x, "x"), _chk(w_packed.blob, "w"), _opt(scale, "scale"), _opt(shift, "shift"), _opt(up_add, "up_add"),
-                  _chk(y, "y"), _opt(ysq_absmax, "ysq_absmax"), N, H, W, Ci, Co, int(relu), _stream()), "conv1x1_fwd")
+    _lib.call("rcmvs_conv1x1_mfma_fwd" if mfma else "rcmvs_conv1x1_fwd", _chk(x, "x"), _chk(w_packed.blob, "w"), _opt(scale, "scale"), _opt(shift, "shift"),
+              _opt(up_add, "up_add"), _chk(y, "y"), _opt(ysq_absmax, "ysq_absmax"), N, H, W, Ci, Co, int(relu), _stream())
     return y
 
 
@@ -472,8 +453,8 @@ def conv2d_rgb(x, w_packed, scale=None, shift=None, relu=False):
     if C != 3 or w_packed.ci != 4 or w_packed.co != 8 or w_packed.k != 3:
         raise _lib.RcmvsError(f"conv2d_rgb: expected a (N,3,H,W) input and a 3 -> 8 3x3 weight packed to 4 input channels (got {tuple(x.shape)}, {w_packed.ci} -> {w_packed.co}, k={w_packed.k})")
     y = torch.empty((N, H, W, 8), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_conv2d_fwd(_chk(x, "x"), _chk(w_packed.blob, "w"), _opt(scale, "scale"), _opt(shift, "shift"), None,
-                                            _chk(y, "y"), N, H, W, 3, 8, 3, 1, int(relu), _stream()), "conv2d_fwd")
+    _lib.call("rcmvs_conv2d_fwd", _chk(x, "x"), _chk(w_packed.blob, "w"), _opt(scale, "scale"), _opt(shift, "shift"), None,
+              _chk(y, "y"), N, H, W, 3, 8, 3, 1, int(relu), _stream())
     return y
 
 
@@ -484,7 +465,7 @@ def pack_conv2d_tile(w):
         raise _lib.RcmvsError("pack_conv2d_tile: built for 32 -> 16 and 32 -> 32 3x3 layers")
     lib = _lib.load()
     img = torch.empty(int(lib.rcmvs_conv2d_tile_weight_floats(Co)), device=w.device, dtype=torch.float32)
-    _lib.check(lib.rcmvs_pack_conv2d_tile(_chk(w.detach().float().contiguous(), "w"), _chk(img, "image"), Co, _stream()), "pack_conv2d_tile")
+    _lib.call("rcmvs_pack_conv2d_tile", _chk(w.detach().float().contiguous(), "w"), _chk(img, "image"), Co, _stream())
     return img
 
 
@@ -498,8 +479,8 @@ def conv2d_tile(x, image, scale=None, shift=None, relu=False, s2d=False, ysq_abs
         raise _lib.RcmvsError(f"conv2d_tile: unexpected input {tuple(x.shape)} (s2d={s2d}) or image of {image.numel()} floats")
     H, W = (Hx // 2, Wx // 2) if s2d else (Hx, Wx)
     y = torch.empty((N, H, W, Co), device=x.device, dtype=torch.float32)
-    _lib.check(lib.rcmvs_conv2d_tile_fwd(_chk(x, "x"), _chk(image, "image"), _opt(scale, "scale"), _opt(shift, "shift"), _chk(y, "y"), N, H, W, Co, int(s2d), int(relu),
-                                         _opt(ysq_absmax, "ysq_absmax"), _stream()), "conv2d_tile_fwd")
+    _lib.call("rcmvs_conv2d_tile_fwd", _chk(x, "x"), _chk(image, "image"), _opt(scale, "scale"), _opt(shift, "shift"), _chk(y, "y"), N, H, W, Co, int(s2d), int(relu),
+              _opt(ysq_absmax, "ysq_absmax"), _stream())
     return y
 
 
@@ -509,7 +490,7 @@ def pack_conv2d_stem(wb):
         raise _lib.RcmvsError("pack_conv2d_stem: built for an 8 -> 8 3x3 second layer")
     lib = _lib.load()
     img = torch.empty(int(lib.rcmvs_conv2d_stem_weight_floats()), device=wb.device, dtype=torch.float32)
-    _lib.check(lib.rcmvs_pack_conv2d_stem(_chk(wb.detach().float().contiguous(), "wb"), _chk(img, "image"), _stream()), "pack_conv2d_stem")
+    _lib.call("rcmvs_pack_conv2d_stem", _chk(wb.detach().float().contiguous(), "wb"), _chk(img, "image"), _stream())
     return img
 
 
@@ -520,8 +501,8 @@ def conv2d_stem(x, w_a_packed, scale_a, shift_a, image_b, scale_b, shift_b):
     if C != 3 or w_a_packed.ci != 4 or w_a_packed.co != 8 or w_a_packed.k != 3:
         raise _lib.RcmvsError(f"conv2d_stem: expected a (N,3,H,W) input and a 3 -> 8 3x3 weight packed to 4 input channels (got {tuple(x.shape)}, {w_a_packed.ci} -> {w_a_packed.co}, k={w_a_packed.k})")
     y = torch.empty((N, H, W, 8), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_conv2d_stem_fwd(_chk(x, "x"), _chk(w_a_packed.blob, "w_a"), _chk(scale_a, "scale_a"), _chk(shift_a, "shift_a"), _chk(image_b, "image_b"),
-                                                 _chk(scale_b, "scale_b"), _chk(shift_b, "shift_b"), _chk(y, "y"), N, H, W, _stream()), "conv2d_stem_fwd")
+    _lib.call("rcmvs_conv2d_stem_fwd", _chk(x, "x"), _chk(w_a_packed.blob, "w_a"), _chk(scale_a, "scale_a"), _chk(shift_a, "shift_a"), _chk(image_b, "image_b"),
+              _chk(scale_b, "scale_b"), _chk(shift_b, "shift_b"), _chk(y, "y"), N, H, W, _stream())
     return y
 
 
@@ -534,12 +515,12 @@ def fpn_out_fused(lat, up, w_inner_packed, b_inner, w_out_packed):
     if tuple(up.shape) != (N, H // 2, W // 2, CM):
         raise _lib.RcmvsError(f"fpn_out_fused: up {tuple(up.shape)} does not match half of {tuple(lat.shape)} with {CM} channels")
     y = torch.empty((N, H, W, CO), device=lat.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_fpn_out_fused(_chk(lat, "lat"), _chk(up, "up"), _chk(w_inner_packed.blob, "w_inner"), _chk(b_inner, "b_inner"),
-                                               _chk(w_out_packed.blob, "w_out"), _chk(y, "y"), N, H, W, CL, CM, CO, _stream()), "fpn_out_fused")
+    _lib.call("rcmvs_fpn_out_fused", _chk(lat, "lat"), _chk(up, "up"), _chk(w_inner_packed.blob, "w_inner"), _chk(b_inner, "b_inner"),
+              _chk(w_out_packed.blob, "w_out"), _chk(y, "y"), N, H, W, CL, CM, CO, _stream())
     return y
 
 
-FPN_FOLDED_FLOATS = 4744      # RCMVS_FPN_FOLDED_FLOATS of include/rcmvs.h
+FPN_FOLDED_FLOATS = _lib.CONSTANTS["RCMVS_FPN_FOLDED_FLOATS"]
 
 
 def pack_fpn_folded(w_inner, b_inner, w_out):
@@ -572,7 +553,7 @@ def pack_fpn_folded_mfma(tables):
     if tables.numel() != FPN_FOLDED_FLOATS:
         raise _lib.RcmvsError("pack_fpn_folded_mfma: expects the tables of pack_fpn_folded")
     img = torch.empty((_lib.load().rcmvs_fpn_folded_mfma_floats(),), device=tables.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_fpn_folded_mfma_pack(_chk(tables, "tables"), _chk(img, "image"), _stream()), "fpn_folded_mfma_pack")
+    _lib.call("rcmvs_fpn_folded_mfma_pack", _chk(tables, "tables"), _chk(img, "image"), _stream())
     return img
 
 
@@ -585,8 +566,8 @@ def fpn_out_folded(lat, up, tables, ysq_absmax=None):
     if CL != 8 or tuple(up.shape) != (N, H // 2, W // 2, 32) or not (mfma or tables.numel() == FPN_FOLDED_FLOATS):
         raise _lib.RcmvsError(f"fpn_out_folded: lat {tuple(lat.shape)} / up {tuple(up.shape)} / {tables.numel()} table floats do not fit 8 -> 32 -> 8")
     y = torch.empty((N, H, W, 8), device=lat.device, dtype=torch.float32)
-    fn = _lib.load().rcmvs_fpn_out_folded_mfma if mfma else _lib.load().rcmvs_fpn_out_folded
-    _lib.check(fn(_chk(lat, "lat"), _chk(up, "up"), _chk(tables, "tables"), _chk(y, "y"), _opt(ysq_absmax, "ysq_absmax"), N, H, W, _stream()), "fpn_out_folded")
+    _lib.call("rcmvs_fpn_out_folded_mfma" if mfma else "rcmvs_fpn_out_folded", _chk(lat, "lat"), _chk(up, "up"), _chk(tables, "tables"), _chk(y, "y"),
+              _opt(ysq_absmax, "ysq_absmax"), N, H, W, _stream())
     return y
 
 
@@ -608,10 +589,9 @@ def depth_head(x8, w_prob_packed, planes, want_prob=False, x_absmax=None):
     conf = torch.empty((B, h, w), device=x8.device, dtype=torch.float32)
     one_launch = D == 8 and not (DEPTH_HEAD_IMPL & 1)
     prob = None if one_launch and not want_prob else torch.empty((B, D, h, w), device=x8.device, dtype=torch.float32)     # logit scratch -> probabilities
-    _lib.check(_lib.load().rcmvs_depth_head_scaled_fwd(_chk(x8, "x8"), _opt(x_absmax, "x_absmax"), _chk(w_prob_packed.blob, "w_prob"), _chk(planes, "planes"),
-                                                       _chk(depth, "depth"), _chk(conf, "conf"), _opt(prob, "prob"), B, D, h, w,
-                                                       DEPTH_HEAD_IMPL | (0 if want_prob else 8), _stream()),
-               "depth_head_scaled_fwd")
+    _lib.call("rcmvs_depth_head_scaled_fwd", _chk(x8, "x8"), _opt(x_absmax, "x_absmax"), _chk(w_prob_packed.blob, "w_prob"), _chk(planes, "planes"),
+              _chk(depth, "depth"), _chk(conf, "conf"), _opt(prob, "prob"), B, D, h, w,
+              DEPTH_HEAD_IMPL | (0 if want_prob else 8), _stream())
     return (depth, conf, prob) if want_prob else (depth, conf)
 
 
@@ -631,11 +611,10 @@ def conv11_prob(t, t_absmax, w11_packed, scale, shift, res, res_absmax, coef, w_
         conf = torch.empty((B, 2 * Ht, 2 * Wt), device=t.device, dtype=torch.float32)
     else:
         logits = torch.empty((B, 2 * Dt, 2 * Ht, 2 * Wt), device=t.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_conv11_prob_fwd(_chk(t, "t"), _chk(t_absmax, "t_absmax"), _chk(w11_packed.blob, "w11"), _chk(scale, "scale"),
-                                                 _chk(shift, "shift"), _chk(res, "res"), _chk(res_absmax, "res_absmax"), _chk(coef, "coef"),
-                                                 _chk(w_prob_packed.blob, "w_prob"), _opt(logits, "logits"), _opt(planes if fused else None, "planes"),
-                                                 _opt(depth, "depth"), _opt(conf, "conf"), B, Dt, Ht, Wt, int(zchunk), _stream()),
-               "conv11_prob_fwd")
+    _lib.call("rcmvs_conv11_prob_fwd", _chk(t, "t"), _chk(t_absmax, "t_absmax"), _chk(w11_packed.blob, "w11"), _chk(scale, "scale"),
+              _chk(shift, "shift"), _chk(res, "res"), _chk(res_absmax, "res_absmax"), _chk(coef, "coef"),
+              _chk(w_prob_packed.blob, "w_prob"), _opt(logits, "logits"), _opt(planes if fused else None, "planes"),
+              _opt(depth, "depth"), _opt(conf, "conf"), B, Dt, Ht, Wt, int(zchunk), _stream())
     if fused:
         return depth, conf
     if planes is not None:
@@ -648,8 +627,8 @@ def softmax_head(logits, planes, keep_prob=False):
     B, D, h, w = logits.shape
     depth = torch.empty((B, h, w), device=logits.device, dtype=torch.float32)
     conf = torch.empty((B, h, w), device=logits.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_softmax_head_fwd(_chk(logits, "logits"), _chk(planes, "planes"), _chk(depth, "depth"), _chk(conf, "conf"),
-                                                  B, D, h, w, int(bool(keep_prob)), _stream()), "softmax_head_fwd")
+    _lib.call("rcmvs_softmax_head_fwd", _chk(logits, "logits"), _chk(planes, "planes"), _chk(depth, "depth"), _chk(conf, "conf"),
+              B, D, h, w, int(bool(keep_prob)), _stream())
     return depth, conf
 
 
@@ -659,8 +638,7 @@ def resize_planes(x, out_planes, pad_channels_to=None):
     B, C, D, h, w = x.shape
     Cp = C if pad_channels_to is None else pad_channels_to
     y = torch.empty((B, out_planes, h, w, Cp), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_resize_planes_fwd(_chk(x, "x"), _chk(y, "y"), B, C, Cp, D, out_planes, h, w, _stream()),
-               "resize_planes_fwd")
+    _lib.call("rcmvs_resize_planes_fwd", _chk(x, "x"), _chk(y, "y"), B, C, Cp, D, out_planes, h, w, _stream())
     return y
 
 
@@ -671,10 +649,10 @@ def gu_sample(pseudo_depth, img0, pix, eps, u, cam):
     dev = eps.device
     f = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
     z, pts, ndc, dirs, rdepth, target = f(N, S), f(N, S, 3), f(N, S, 3), f(N, 3), f(N), f(N, 3)
-    _lib.check(_lib.load().rcmvs_gu_sample_fwd(_chk(pseudo_depth, "pseudo_depth"), _chk(img0, "img0"), _chk(pix, "pix", torch.int32),
-                                               _chk(eps, "eps"), _chk(u, "u"), _chk(cam, "cam"), _chk(z, "z"), _chk(pts, "pts"),
-                                               _chk(ndc, "ndc"), _chk(dirs, "dirs"), _chk(rdepth, "rays_depth"), _chk(target, "target"),
-                                               N, S, H, W, _stream()), "gu_sample_fwd")
+    _lib.call("rcmvs_gu_sample_fwd", _chk(pseudo_depth, "pseudo_depth"), _chk(img0, "img0"), _chk(pix, "pix", torch.int32),
+              _chk(eps, "eps"), _chk(u, "u"), _chk(cam, "cam"), _chk(z, "z"), _chk(pts, "pts"),
+              _chk(ndc, "ndc"), _chk(dirs, "dirs"), _chk(rdepth, "rays_depth"), _chk(target, "target"),
+              N, S, H, W, _stream())
     return z, pts, ndc, dirs, rdepth, target
 
 
@@ -686,9 +664,8 @@ def point_feats(volume_cl, imgs, poses, pts, ndc, ldf=32):
     nimg, _, H, W = imgs.shape
     M = pts.shape[0] * pts.shape[1]
     feat = torch.empty((M, ldf), device=pts.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_point_feats_fwd(_chk(volume_cl, "volume"), _chk(imgs, "imgs"), _chk(poses, "poses"), _chk(pts, "pts"),
-                                                 _chk(ndc, "ndc"), _chk(feat, "feat"), M, Dv, hv, wv, nimg, H, W, ldf, _stream()),
-               "point_feats_fwd")
+    _lib.call("rcmvs_point_feats_fwd", _chk(volume_cl, "volume"), _chk(imgs, "imgs"), _chk(poses, "poses"), _chk(pts, "pts"),
+              _chk(ndc, "ndc"), _chk(feat, "feat"), M, Dv, hv, wv, nimg, H, W, ldf, _stream())
     return feat
 
 
@@ -705,7 +682,7 @@ def pack_nerf_weights(named):
         tensors += [w.detach().contiguous().float(), b.detach().contiguous().float()]
     arr = (ctypes.c_void_p * 22)(*[_chk(t, "nerf weight").value for t in tensors])
     blob = torch.empty((lib.rcmvs_nerf_weight_floats(),), device=tensors[0].device, dtype=torch.float32)
-    _lib.check(lib.rcmvs_pack_nerf_weights(arr, _chk(blob, "blob"), _stream()), "pack_nerf_weights")
+    _lib.call("rcmvs_pack_nerf_weights", arr, _chk(blob, "blob"), _stream())
     return blob
 
 
@@ -716,8 +693,8 @@ def nerf_mlp(ndc, feat, dirs, w2c_ref, blob):
     M = N * S
     ws = torch.empty((lib.rcmvs_nerf_workspace_floats(M),), device=ndc.device, dtype=torch.float32)
     raw = torch.empty((N, S, 4), device=ndc.device, dtype=torch.float32)
-    _lib.check(lib.rcmvs_nerf_mlp_fwd(_chk(ndc, "ndc"), _chk(feat, "feat"), feat.shape[1], _chk(dirs, "dirs"), _chk(w2c_ref, "w2c_ref"),
-                                      _chk(blob, "weights"), _chk(ws, "workspace"), _chk(raw, "raw"), N, S, _stream()), "nerf_mlp_fwd")
+    _lib.call("rcmvs_nerf_mlp_fwd", _chk(ndc, "ndc"), _chk(feat, "feat"), feat.shape[1], _chk(dirs, "dirs"), _chk(w2c_ref, "w2c_ref"),
+              _chk(blob, "weights"), _chk(ws, "workspace"), _chk(raw, "raw"), N, S, _stream())
     return raw
 
 
@@ -730,8 +707,7 @@ def nerf_mlp_embedded(x, blob):
     ws = torch.empty((lib.rcmvs_nerf_workspace_floats(M),), device=x.device, dtype=torch.float32)
     feat = torch.empty((M, 32), device=x.device, dtype=torch.float32)
     raw = torch.empty((M, 4), device=x.device, dtype=torch.float32)
-    _lib.check(lib.rcmvs_nerf_mlp_embedded_fwd(_chk(x, "x"), ldx, _chk(blob, "weights"), _chk(ws, "workspace"), _chk(feat, "feat"), _chk(raw, "raw"), M, _stream()),
-               "nerf_mlp_embedded_fwd")
+    _lib.call("rcmvs_nerf_mlp_embedded_fwd", _chk(x, "x"), ldx, _chk(blob, "weights"), _chk(ws, "workspace"), _chk(feat, "feat"), _chk(raw, "raw"), M, _stream())
     return raw
 
 
@@ -743,6 +719,6 @@ def composite(raw, z):
     depth = torch.empty((N,), device=dev, dtype=torch.float32)
     weights = torch.empty((N, S), device=dev, dtype=torch.float32)
     alpha = torch.empty((N, S), device=dev, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_composite_fwd(_chk(raw, "raw"), _chk(z, "z"), _chk(rgb, "rgb"), _chk(depth, "depth"),
-                                               _chk(weights, "weights"), _chk(alpha, "alpha"), N, S, _stream()), "composite_fwd")
+    _lib.call("rcmvs_composite_fwd", _chk(raw, "raw"), _chk(z, "z"), _chk(rgb, "rgb"), _chk(depth, "depth"),
+              _chk(weights, "weights"), _chk(alpha, "alpha"), N, S, _stream())
     return rgb, depth, weights, alpha

@@ -25,30 +25,30 @@ from .ops import _chk, _opt, _stream
 # --------------------------------------------------------------------------------------- thin wrappers
 def bn_stats(x, sums):
     C = x.shape[-1]
-    _lib.check(_lib.load().rcmvs_bn_stats(_chk(x, "x"), _chk(sums, "sums", torch.float64), x.numel() // C, C, _stream()), "bn_stats")
+    _lib.call("rcmvs_bn_stats", _chk(x, "x"), _chk(sums, "sums", torch.float64), x.numel() // C, C, _stream())
 
 
 def scale_shift_relu(x, scale, shift, residual, relu, out=None):
     C = x.shape[-1]
     y = torch.empty_like(x) if out is None else out
-    _lib.check(_lib.load().rcmvs_scale_shift_relu(_chk(x, "x"), _opt(scale, "scale"), _opt(shift, "shift"), _opt(residual, "residual"),
-                                                  _chk(y, "y"), x.numel() // C, C, int(bool(relu)), _stream()), "scale_shift_relu")
+    _lib.call("rcmvs_scale_shift_relu", _chk(x, "x"), _opt(scale, "scale"), _opt(shift, "shift"), _opt(residual, "residual"),
+              _chk(y, "y"), x.numel() // C, C, int(bool(relu)), _stream())
     return y
 
 
 def bn_bwd_reduce(y, dz, scale, shift, mean, invstd, sums, relu):
     C = y.shape[-1]
-    _lib.check(_lib.load().rcmvs_bn_bwd_reduce(_chk(y, "y"), _chk(dz, "dz"), _chk(scale, "scale"), _chk(shift, "shift"),
-                                               _chk(mean, "mean"), _chk(invstd, "invstd"), _chk(sums, "sums", torch.float64),
-                                               y.numel() // C, C, int(bool(relu)), _stream()), "bn_bwd_reduce")
+    _lib.call("rcmvs_bn_bwd_reduce", _chk(y, "y"), _chk(dz, "dz"), _chk(scale, "scale"), _chk(shift, "shift"),
+              _chk(mean, "mean"), _chk(invstd, "invstd"), _chk(sums, "sums", torch.float64),
+              y.numel() // C, C, int(bool(relu)), _stream())
 
 
 def bn_bwd_apply(y, dz, scale, shift, mean, invstd, coef, relu, out=None):
     C = y.shape[-1]
     dy = torch.empty_like(y) if out is None else out
-    _lib.check(_lib.load().rcmvs_bn_bwd_apply(_chk(y, "y"), _chk(dz, "dz"), _chk(scale, "scale"), _chk(shift, "shift"),
-                                              _chk(mean, "mean"), _chk(invstd, "invstd"), _chk(coef, "coef"), _chk(dy, "dy"),
-                                              y.numel() // C, C, int(bool(relu)), _stream()), "bn_bwd_apply")
+    _lib.call("rcmvs_bn_bwd_apply", _chk(y, "y"), _chk(dz, "dz"), _chk(scale, "scale"), _chk(shift, "shift"),
+              _chk(mean, "mean"), _chk(invstd, "invstd"), _chk(coef, "coef"), _chk(dy, "dy"),
+              y.numel() // C, C, int(bool(relu)), _stream())
     return dy
 
 
@@ -60,8 +60,7 @@ def conv3d_wgrad(x, dy, stride, out=None):
     if tuple(dy.shape[:4]) != exp:
         raise _lib.RcmvsError(f"conv3d_wgrad: dy {tuple(dy.shape)} does not match x {tuple(x.shape)} at stride {stride}")
     dw = torch.zeros((27, Ci, Co), device=x.device, dtype=torch.float32) if out is None else out
-    _lib.check(_lib.load().rcmvs_conv3d_wgrad(_chk(x, "x"), _chk(dy, "dy"), _chk(dw, "dw"), B, D, H, W, Ci, Co, stride, _stream()),
-               "conv3d_wgrad")
+    _lib.call("rcmvs_conv3d_wgrad", _chk(x, "x"), _chk(dy, "dy"), _chk(dw, "dw"), B, D, H, W, Ci, Co, stride, _stream())
     return dw
 
 
@@ -84,7 +83,7 @@ def _wgrad_to_param_layout(big, small, stride, w_shape):
     ent[1] = False
     conv3d_wgrad(big, small, stride, out=buf)
     out = torch.empty(tuple(w_shape), device=big.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_wgrad_finish(_chk(buf, "packed"), _chk(out, "dw"), P, Q, int(w_shape[1]), _stream()), "wgrad_finish")
+    _lib.call("rcmvs_wgrad_finish", _chk(buf, "packed"), _chk(out, "dw"), P, Q, int(w_shape[1]), _stream())
     ent[1] = True
     return out
 
@@ -94,16 +93,15 @@ def conv3d_dgrad_c1(dy, w):
     B, D, H, W = dy.shape
     Ci = w.shape[1]
     dx = torch.empty((B, D, H, W, Ci), device=dy.device, dtype=torch.float32)
-    _lib.check(_lib.load().rcmvs_conv3d_dgrad_c1(_chk(dy, "dy"), _chk(w, "w"), _chk(dx, "dx"), B, D, H, W, Ci, _stream()),
-               "conv3d_dgrad_c1")
+    _lib.call("rcmvs_conv3d_dgrad_c1", _chk(dy, "dy"), _chk(w, "w"), _chk(dx, "dx"), B, D, H, W, Ci, _stream())
     return dx
 
 
 def depth_head_bwd(prob, planes, depth, gdepth):
     B, D, h, w = prob.shape
     dl = torch.empty_like(prob)
-    _lib.check(_lib.load().rcmvs_depth_head_bwd(_chk(prob, "prob"), _chk(planes, "planes"), _chk(depth, "depth"), _chk(gdepth, "gdepth"),
-                                                _chk(dl, "dlogits"), B, D, h, w, _stream()), "depth_head_bwd")
+    _lib.call("rcmvs_depth_head_bwd", _chk(prob, "prob"), _chk(planes, "planes"), _chk(depth, "depth"), _chk(gdepth, "gdepth"),
+              _chk(dl, "dlogits"), B, D, h, w, _stream())
     return dl
 
 
@@ -232,7 +230,6 @@ class ConvBnReluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, gamma, beta, residual, running_mean, running_var, cfg):
         x = x.contiguous()
-        lib = _lib.load()
         y = _conv_raw(x, w.detach(), cfg["transposed"], cfg["stride"], _param_of(w))
         C = y.shape[-1]
         S = int(cfg.get("segments", 1))
@@ -251,10 +248,10 @@ class ConvBnReluFn(torch.autograd.Function):
                 dist.all_reduce(pack[sgm], group=cfg["group"])
             rs = None if res is None else res[sgm * nb:(sgm + 1) * nb]
             zs = z[sgm * nb:(sgm + 1) * nb]
-            _lib.check(lib.rcmvs_bn_norm_fwd(_chk(ys, "y"), ptr(pack[sgm]), ptr(spent[sgm]), _chk(g32, "gamma"), _chk(b32, "beta"),
-                                             float(cfg["eps"]), float(cfg.get("momentum", 0.0)), ptr(stats[sgm]), ptr(cnt[sgm:]),
-                                             _opt(running_mean, "running_mean"), _opt(running_var, "running_var"), _opt(rs, "residual"),
-                                             _chk(zs, "z"), ys.numel() // C, C, int(bool(cfg["relu"])), _stream()), "bn_norm_fwd")
+            _lib.call("rcmvs_bn_norm_fwd", _chk(ys, "y"), ptr(pack[sgm]), ptr(spent[sgm]), _chk(g32, "gamma"), _chk(b32, "beta"),
+                      float(cfg["eps"]), float(cfg.get("momentum", 0.0)), ptr(stats[sgm]), ptr(cnt[sgm:]),
+                      _opt(running_mean, "running_mean"), _opt(running_var, "running_var"), _opt(rs, "residual"),
+                      _chk(zs, "z"), ys.numel() // C, C, int(bool(cfg["relu"])), _stream())
         done()                                                                   # every segment's `spent` row has its clearing launch enqueued
         ctx.save_for_backward(x, w, y, stats, cnt)
         ctx.cfg = cfg
@@ -281,9 +278,9 @@ class ConvBnReluFn(torch.autograd.Function):
             if cfg.get("group") is not None:
                 tot = sums[sgm].clone()
                 dist.all_reduce(tot, group=cfg["group"])
-            _lib.check(_lib.load().rcmvs_bn_norm_bwd(_chk(y[sl], "y"), _chk(dz[sl], "dz"), ptr(stats[sgm]), ptr(sums[sgm]), ptr(tot), ptr(cnt[sgm:]),
-                                                     ptr(spent[sgm]), ptr(out[sgm, 0]), ptr(out[sgm, 1]), _chk(dy[sl], "dy"), y[sl].numel() // C, C,
-                                                     int(bool(cfg["relu"])), _stream()), "bn_norm_bwd")
+            _lib.call("rcmvs_bn_norm_bwd", _chk(y[sl], "y"), _chk(dz[sl], "dz"), ptr(stats[sgm]), ptr(sums[sgm]), ptr(tot), ptr(cnt[sgm:]),
+                      ptr(spent[sgm]), ptr(out[sgm, 0]), ptr(out[sgm, 1]), _chk(dy[sl], "dy"), y[sl].numel() // C, C,
+                      int(bool(cfg["relu"])), _stream())
         done()
         dgamma, dbeta = (out[0, 0], out[0, 1]) if S == 1 else (out[:, 0].sum(0), out[:, 1].sum(0))
         dx = _conv_dgrad(dy, w, cfg["transposed"], cfg["stride"], x.shape[-1], _param_of(w)) if ctx.needs_input_grad[0] else None
@@ -366,8 +363,7 @@ class ResizePlanesFn(torch.autograd.Function):
         B, C, D, h, w = ctx.shape
         g = g.contiguous()
         gx = torch.empty(ctx.shape, device=g.device, dtype=torch.float32)
-        _lib.check(_lib.load().rcmvs_resize_planes_bwd(_chk(g, "g"), _chk(gx, "gx"), B, C, g.shape[-1], D, g.shape[1], h, w, _stream()),
-                   "resize_planes_bwd")
+        _lib.call("rcmvs_resize_planes_bwd", _chk(g, "g"), _chk(gx, "gx"), B, C, g.shape[-1], D, g.shape[1], h, w, _stream())
         return gx, None, None
 
 
@@ -390,8 +386,8 @@ class PointFeatsFn(torch.autograd.Function):
         Dv, hv, wv, _ = ctx.vshape
         gfeat = gfeat.contiguous()
         gvol = torch.zeros(ctx.vshape, device=gfeat.device, dtype=torch.float32)
-        _lib.check(_lib.load().rcmvs_point_feats_bwd(_chk(ndc, "ndc"), _chk(gfeat, "grad_feat"), _chk(gvol, "grad_volume"),
-                                                     gfeat.shape[0], Dv, hv, wv, gfeat.shape[1], _stream()), "point_feats_bwd")
+        _lib.call("rcmvs_point_feats_bwd", _chk(ndc, "ndc"), _chk(gfeat, "grad_feat"), _chk(gvol, "grad_volume"),
+                  gfeat.shape[0], Dv, hv, wv, gfeat.shape[1], _stream())
         return gvol, None, None, None, None, None
 
 
@@ -411,9 +407,8 @@ class CompositeFn(torch.autograd.Function):
         c = lambda t: None if t is None else t.contiguous()
         g_rgb, g_depth, g_w, g_alpha = c(g_rgb), c(g_depth), c(g_w), c(g_alpha)
         graw = torch.empty_like(raw)
-        _lib.check(_lib.load().rcmvs_composite_bwd(_chk(raw, "raw"), _chk(z, "z"), _opt(g_rgb, "g_rgb"), _opt(g_depth, "g_depth"),
-                                                   _opt(g_w, "g_w"), _opt(g_alpha, "g_alpha"), _chk(graw, "grad_raw"), N, S, _stream()),
-                   "composite_bwd")
+        _lib.call("rcmvs_composite_bwd", _chk(raw, "raw"), _chk(z, "z"), _opt(g_rgb, "g_rgb"), _opt(g_depth, "g_depth"),
+                  _opt(g_w, "g_w"), _opt(g_alpha, "g_alpha"), _chk(graw, "grad_raw"), N, S, _stream())
         return graw, None
 
 
@@ -432,13 +427,13 @@ class NerfMlpFn(torch.autograd.Function):
         ps = [p.detach().contiguous().float() for p in params]
         arr = (ctypes.c_void_p * 22)(*[_chk(t, "nerf weight").value for t in ps])
         blob = torch.empty((lib.rcmvs_nerf_weight_floats(),), device=ndc.device, dtype=torch.float32)
-        _lib.check(lib.rcmvs_pack_nerf_weights(arr, _chk(blob, "blob"), _stream()), "pack_nerf_weights")
+        _lib.call("rcmvs_pack_nerf_weights", arr, _chk(blob, "blob"), _stream())
         feat = feat.detach().contiguous().clone()            # the forward zeroes its padding columns in place
         tws = torch.empty((lib.rcmvs_nerf_train_workspace_floats(M),), device=ndc.device, dtype=torch.float32)
         raw = torch.empty((N, S, 4), device=ndc.device, dtype=torch.float32)
-        _lib.check(lib.rcmvs_nerf_mlp_train_fwd(_chk(ndc.contiguous(), "ndc"), _chk(feat, "feat"), feat.shape[1], _chk(dirs.contiguous(), "dirs"),
-                                                _chk(w2c_ref.contiguous(), "w2c_ref"), _chk(blob, "weights"), _chk(tws, "workspace"),
-                                                _chk(raw, "raw"), N, S, _stream()), "nerf_mlp_train_fwd")
+        _lib.call("rcmvs_nerf_mlp_train_fwd", _chk(ndc.contiguous(), "ndc"), _chk(feat, "feat"), feat.shape[1], _chk(dirs.contiguous(), "dirs"),
+                  _chk(w2c_ref.contiguous(), "w2c_ref"), _chk(blob, "weights"), _chk(tws, "workspace"),
+                  _chk(raw, "raw"), N, S, _stream())
         ctx.save_for_backward(feat, tws, raw, *ps)
         ctx.dims = (N, S)
         return raw
@@ -462,8 +457,8 @@ class NerfMlpFn(torch.autograd.Function):
         grads = [torch.empty_like(p) for p in ps]
         warr = (ctypes.c_void_p * 22)(*[_chk(t, "nerf weight").value for t in ps])
         garr = (ctypes.c_void_p * 22)(*[_chk(t, "nerf grad").value for t in grads])
-        _lib.check(lib.rcmvs_nerf_mlp_bwd(warr, _chk(feat, "feat"), feat.shape[1], _chk(tws, "workspace"), _chk(raw, "raw"), _chk(graw, "grad_raw"),
-                                          _chk(gws, "scratch"), _chk(dfeat, "grad_feat"), garr, N, S, _stream()), "nerf_mlp_bwd")
+        _lib.call("rcmvs_nerf_mlp_bwd", warr, _chk(feat, "feat"), feat.shape[1], _chk(tws, "workspace"), _chk(raw, "raw"), _chk(graw, "grad_raw"),
+                  _chk(gws, "scratch"), _chk(dfeat, "grad_feat"), garr, N, S, _stream())
         return (None, dfeat, None, None, *grads)
 
 

@@ -26,8 +26,8 @@ SCALAR_KEYS = ("loss", "depth_loss", "abs_depth_error", "thres2mm_error", "thres
 SUM_KEYS = ("sl1_stage1", "sl1_stage2", "sl1_stage3", "sum_abs_error", "band2mm_sum", "band4mm_sum", "band8mm_sum")
 COUNT_KEYS = ("n_stage1", "n_stage2", "n_stage3", "count_gt2mm", "count_gt4mm", "count_gt8mm", "band2mm_count", "band4mm_count",
               "band8mm_count")
-RECORD = 32                     # RCMVS_DM_RECORD: doubles per table row = the 12 scalars, the 16 raw sums / counts, 4 zeros
-RAW = 12                        # RCMVS_DM_RAW
+RECORD = _lib.CONSTANTS["RCMVS_DM_RECORD"]      # doubles per table row = the 12 scalars, the 16 raw sums / counts, 4 zeros
+RAW = _lib.CONSTANTS["RCMVS_DM_RAW"]            # column of the first raw sum
 DLOSSW = (0.5, 1.0, 2.0)        # --dlossw default, train_rcmvsnet.py:61
 STAGES = ("stage1", "stage2", "stage3")
 THRESHOLDS = (2.0, 4.0, 8.0)
@@ -103,14 +103,15 @@ def _launch(triples, dlossw, table, slot, images, events=None, cached=True):
     args += [ctypes.cast(w, ctypes.c_void_p) if w is not None else ctypes.c_void_p(0), _chk(table, "table", torch.float64), slot,
              _chk(out["depth_est"], "depth_est") if out else ctypes.c_void_p(0), _chk(out["errormap"], "errormap") if out else ctypes.c_void_p(0),
              _chk(ws, "workspace", torch.uint8)]
-    lib = _lib.load()
-    if events is None:
-        rc = lib.rcmvs_depth_metrics(*args, _stream())
-    else:
-        rc = lib.rcmvs_depth_metrics_timed(*args, ctypes.c_void_p(events[0].cuda_event), ctypes.c_void_p(events[1].cuda_event), _stream())
-    if rc != 0:
+    stream = _stream()
+    try:
+        if events is None:
+            _lib.call("rcmvs_depth_metrics", *args, stream)
+        else:
+            _lib.call("rcmvs_depth_metrics_timed", *args, ctypes.c_void_p(events[0].cuda_event), ctypes.c_void_p(events[1].cuda_event), stream)
+    except _lib.RcmvsError:
         _WORKSPACES.pop((str(device), sizes), None)                 # its ticket may be part-drawn: never reuse it
-    _lib.check(rc, "depth_metrics")
+        raise
     return table[slot], out
 
 
