@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librcmvs_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "rcmvs.h")
+EXT_HEADERS = (os.path.join(CSRC, "pc_register.h"),)      # entry-point families declared next to their kernels (same grammar as HEADER)
 
 _lib = None
 
@@ -101,6 +102,28 @@ SIGNATURES, _RESTYPES, CONSTANTS = parse_header(_read_header())
 REQUIRED_VERSION = CONSTANTS["RCMVS_VERSION"]      # the RCMVS_VERSION of the header this binding is derived from
 
 
+def _read_extensions():
+    """EXT_HEADERS -> (name -> argtypes, name -> restype); their integer macros join CONSTANTS.  A name the primary header already has is an error."""
+    signatures, restypes = {}, {}
+    for path in EXT_HEADERS:
+        try:
+            with open(path) as f:
+                sig, res, const = parse_header(f.read())
+        except FileNotFoundError:
+            raise RcmvsError(f"{path} is missing: the binding of its entry points is derived from it") from None
+        for table, add in ((signatures, sig), (CONSTANTS, const)):
+            clash = [k for k in add if k in table or k in SIGNATURES]
+            if clash:
+                raise RcmvsError(f"{path}: {clash[0]} is already declared")
+            table.update(add)
+        restypes.update(res)
+    return signatures, restypes
+
+
+# the extension headers' tables; SIGNATURES stays the primary header's alone
+EXT_SIGNATURES, _EXT_RESTYPES = _read_extensions()
+
+
 def sources():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
 
@@ -135,6 +158,15 @@ def build(force=False, verbose=False):
     return LIB_PATH
 
 
+def bind(lib):
+    """Give every declared entry point of `lib` (the primary header's and the extension headers') its argtypes and restype."""
+    for table, restypes in ((SIGNATURES, _RESTYPES), (EXT_SIGNATURES, _EXT_RESTYPES)):
+        for name, argtypes in table.items():
+            fn = getattr(lib, name)          # AttributeError if the symbol is not exported
+            fn.argtypes = argtypes
+            fn.restype = restypes.get(name, ctypes.c_int)
+
+
 def load():
     """Load the shared library (raises RcmvsError when it has not been built)."""
     global _lib
@@ -145,10 +177,7 @@ def load():
         raise RcmvsError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                          "(hipcc --offload-arch=gfx950). There is no CPU / eager fallback.")
     lib = ctypes.CDLL(path)
-    for name, argtypes in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError if the symbol is not exported
-        fn.argtypes = argtypes
-        fn.restype = _RESTYPES.get(name, ctypes.c_int)
+    bind(lib)
     if lib.rcmvs_version() < REQUIRED_VERSION:
         raise RcmvsError(f"librcmvs_hip.so (version {lib.rcmvs_version()}) is older than this package needs ({REQUIRED_VERSION}): rebuild it")
     _lib = lib

@@ -488,3 +488,79 @@ def write_tanks_tree(root, split="intermediate", scenes=("Family", "Horse"), V=7
             shutil.rmtree(os.path.join(folder, sub), ignore_errors=True)
         out[scene] = scan
     return out
+
+
+def _similarity(axis, deg, scale, shift):
+    """4x4 fp64: scale * (rotation by deg degrees about axis), then the shift"""
+    a = np.asarray(axis, dtype=np.float64)
+    a = a / np.linalg.norm(a)
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    t = math.radians(deg)
+    T = np.eye(4)
+    T[:3, :3] = scale * (np.eye(3) + math.sin(t) * K + (1.0 - math.cos(t)) * (K @ K))
+    T[:3, 3] = shift
+    return T
+
+
+def tanks_fscore_scene(n_gt=5000, n_est=5000, tau=0.01, seed=0, rot_deg=3.0, shift_tau=3.0, scale=1.01, outlier_frac=0.1, missing_frac=0.25,
+                       noise_tau=0.2):
+    """A Tanks-and-Temples-shaped scoring problem with coordinates of order 1.  gt (n_gt,3) fp32: a bumpy closed surface
+    (radius 1 + 0.12 sin 3x cos 2y sin 2z about the origin) sampled at random directions.  est (n_est,3) fp32, in a frame of its
+    own: (1 - outlier_frac) of it are ground-truth points with z below the (1 - missing_frac) quantile (the top of the surface is
+    missing) plus Gaussian noise of noise_tau * tau, the rest uniform outliers in the box; all mapped by T_true^-1.  T_true
+    (est -> gt frame) is a 20 degree, scale 1.7 similarity; init = D T_true with the KNOWN error D: rot_deg degrees about a
+    tilted axis, a shift of shift_tau * tau per axis, scale ``scale``.  volume: a concave (L-shaped) polygon prism about z that
+    cuts one corner of the surface off.  -> dict(gt, est, T_true, init, D, volume=dict(axis, axis_min, axis_max, polygon (m,3)), tau)."""
+    rng = np.random.default_rng(seed)
+    d = rng.normal(size=(n_gt, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    r = 1.0 + 0.12 * np.sin(3.0 * d[:, 0]) * np.cos(2.0 * d[:, 1]) * np.sin(2.0 * d[:, 2] + 0.5)
+    gt = (d * r[:, None]).astype(np.float32)
+    n_out = int(round(outlier_frac * n_est))
+    low = np.flatnonzero(gt[:, 2] < np.quantile(gt[:, 2], 1.0 - missing_frac))
+    pick = low[rng.integers(0, len(low), n_est - n_out)]
+    good = gt[pick].astype(np.float64) + rng.normal(0.0, noise_tau * tau, (n_est - n_out, 3))
+    far = rng.uniform(-1.2, 1.2, (n_out, 3))
+    est_gt_frame = np.concatenate([good, far])[rng.permutation(n_est)]
+    T_true = _similarity((0.3, -0.5, 0.8), 20.0, 1.7, (0.4, -0.2, 0.3))
+    D = _similarity((0.6, 0.3, -0.7), rot_deg, scale, (shift_tau * tau, -shift_tau * tau, 0.5 * shift_tau * tau))
+    inv = np.linalg.inv(T_true)
+    est = (est_gt_frame @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32)
+    polygon = np.array([[-1.3, -1.3], [1.3, -1.3], [1.3, 0.35], [0.4, 0.35], [0.4, 1.3], [-1.3, 1.3]])
+    polygon = np.concatenate([polygon, np.zeros((len(polygon), 1))], 1)
+    volume = {"axis": 2, "axis_min": -0.95, "axis_max": 1.3, "polygon": polygon}
+    return {"gt": gt, "est": est, "T_true": T_true, "init": D @ T_true, "D": D, "volume": volume, "tau": float(tau)}
+
+
+def write_tanks_gt_tree(root, plydir, scenes=("Barn", "Truck"), n_gt=5000, n_est=5000, n_cams=12, seed=0, taus=None):
+    """The five files of every scene as rc_mvsnet_amd.tanks_fscore reads them: <root>/<scene>/<scene>.ply (ground truth),
+    <scene>.json (Open3D's SelectionPolygonVolume), <scene>_trans.txt (the scene's ``init``), <scene>_COLMAP_SfM.log (n_cams
+    camera-to-world poses in the estimate's frame) and <plydir>/<scene>.ply (the estimate).  taus: {scene: tau} (default
+    tanks_fscore.SCENE_TAU).  Returns {scene: tanks_fscore_scene's dict}."""
+    import json
+    import os
+    from .fusion import ply_bytes
+    if taus is None:
+        from .tanks_fscore import SCENE_TAU as taus
+    os.makedirs(plydir, exist_ok=True)
+    out = {}
+    for i, scene in enumerate(scenes):
+        s = tanks_fscore_scene(n_gt=n_gt, n_est=n_est, tau=taus[scene], seed=seed + i)
+        folder = os.path.join(root, scene)
+        os.makedirs(folder, exist_ok=True)
+        grey = np.full((1, 3), 128, dtype=np.uint8)
+        for path, pts in ((os.path.join(folder, f"{scene}.ply"), s["gt"]), (os.path.join(plydir, f"{scene}.ply"), s["est"])):
+            with open(path, "wb") as f:
+                f.write(ply_bytes(pts, np.repeat(grey, len(pts), 0)))
+        v = s["volume"]
+        with open(os.path.join(folder, f"{scene}.json"), "w") as f:
+            json.dump({"axis_max": v["axis_max"], "axis_min": v["axis_min"], "bounding_polygon": v["polygon"].tolist(),
+                       "class_name": "SelectionPolygonVolume", "orthogonal_axis": "XYZ"[v["axis"]], "version_major": 1, "version_minor": 0}, f)
+        np.savetxt(os.path.join(folder, f"{scene}_trans.txt"), s["init"], fmt="%.17g")
+        rng = np.random.default_rng(1000 + seed + i)
+        with open(os.path.join(folder, f"{scene}_COLMAP_SfM.log"), "w") as f:
+            for c in range(n_cams):
+                pose = _similarity(rng.normal(size=3), rng.uniform(0.0, 180.0), 1.0, rng.uniform(-2.0, 2.0, 3))
+                f.write(f"{c} {c} {n_cams}\n" + "".join(" ".join("%.17g" % x for x in row) + "\n" for row in pose))
+        out[scene] = s
+    return out
