@@ -564,3 +564,143 @@ def write_tanks_gt_tree(root, plydir, scenes=("Barn", "Truck"), n_gt=5000, n_est
                 f.write(f"{c} {c} {n_cams}\n" + "".join(" ".join("%.17g" % x for x in row) + "\n" for row in pose))
         out[scene] = s
     return out
+
+
+# ----------------------------------------------------------------------------------------
+# a COLMAP sparse model for rc_mvsnet_amd/colmap_import.py
+# ----------------------------------------------------------------------------------------
+def _rotmat_to_qvec(R):
+    """3x3 rotation -> (w, x, y, z) with w >= 0"""
+    t = np.trace(R)
+    if t > 0:
+        s = math.sqrt(t + 1.0) * 2.0
+        q = np.array([0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s])
+    else:
+        i = int(np.argmax(np.diag(R)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = math.sqrt(1.0 + R[i, i] - R[j, j] - R[k, k]) * 2.0
+        q = np.zeros(4)
+        q[0], q[1 + i], q[1 + j], q[1 + k] = (R[k, j] - R[j, k]) / s, 0.25 * s, (R[j, i] + R[i, j]) / s, (R[k, i] + R[i, k]) / s
+    return q if q[0] >= 0 else -q
+
+
+def colmap_arrays(n_images=6, n_points=400, hw=(64, 96), seed=0, radius=4.0, extent=1.3, arc_deg=60.0, keep=1.0):
+    """Cameras on a ring arc of ``arc_deg`` degrees and radius ``radius`` looking at the origin, n_points uniform in the box
+    [-extent, extent]^3; an image observes the points its frustum holds (inside the hw image, in front), each kept with
+    probability ``keep``.  -> dict: extrinsics (n,4,4), centres (n,3), intrinsics (n,3,3), points (m,3), offsets (n+1,) int64,
+    ids int32 (per image ascending), uv [n] of (c,2) pixel positions, hw."""
+    rng = np.random.default_rng(seed)
+    H, W = hw
+    K = np.array([[1.2 * W, 0.0, W / 2.0], [0.0, 1.212 * W, H / 2.0], [0.0, 0.0, 1.0]])
+    pts = rng.uniform(-extent, extent, (n_points, 3))
+    E, C = np.zeros((n_images, 4, 4)), np.zeros((n_images, 3))
+    lists, uvs, offsets = [], [], np.zeros(n_images + 1, dtype=np.int64)
+    for k in range(n_images):
+        a = math.radians(arc_deg) * (k / max(n_images - 1, 1) - 0.5)
+        c = np.array([radius * math.sin(a), 0.15 * radius * math.sin(3.0 * a + 0.4), -radius * math.cos(a)])
+        z = -c / np.linalg.norm(c)
+        x = np.cross(np.array([0.0, 1.0, 0.0]), z)
+        x /= np.linalg.norm(x)
+        R = np.stack([x, np.cross(z, x), z])
+        E[k, :3, :3], E[k, :3, 3], E[k, 3, 3], C[k] = R, -R @ c, 1.0, c
+        cam = pts @ R.T + E[k, :3, 3]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u = K[0, 0] * cam[:, 0] / cam[:, 2] + K[0, 2]
+            v = K[1, 1] * cam[:, 1] / cam[:, 2] + K[1, 2]
+        seen = (cam[:, 2] > 0) & (u >= 0) & (u < W) & (v >= 0) & (v < H)
+        if keep < 1.0:
+            seen &= rng.random(n_points) < keep
+        idx = np.flatnonzero(seen).astype(np.int32)
+        lists.append(idx)
+        uvs.append(np.stack([u[idx], v[idx]], 1))
+        offsets[k + 1] = offsets[k] + len(idx)
+    return {"extrinsics": E, "centres": C, "intrinsics": np.broadcast_to(K, (n_images, 3, 3)).copy(), "points": pts, "offsets": offsets,
+            "ids": np.concatenate(lists).astype(np.int32), "uv": uvs, "hw": (H, W)}
+
+
+def colmap_model(n_images=6, n_points=400, hw=(64, 96), seed=0, camera_model="PINHOLE", ext="jpg", **kwargs):
+    """colmap_arrays as COLMAP's records, with what a reader has to cope with: image ids 10, 12, ... listed in shuffled order, point
+    ids 5, 8, ... listed in shuffled order, 2-D points in shuffled order with unmatched ones (point3D_id -1) and one observation
+    listed twice.  -> dict(cameras, images, points, truth=the colmap_arrays dict in renumbered order)."""
+    A = colmap_arrays(n_images, n_points, hw, seed, **kwargs)
+    rng = np.random.default_rng(seed + 7)
+    H, W = hw
+    K = A["intrinsics"][0]
+    if camera_model == "SIMPLE_PINHOLE":
+        A["intrinsics"][:, 1, 1] = K[0, 0]
+        params = [K[0, 0], K[0, 2], K[1, 2]]
+    else:
+        params = [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]
+    cameras = [{"id": 3, "model": camera_model, "width": W, "height": H, "params": [float(p) for p in params]}]
+    p2d_dtype = np.dtype([("x", "<f8"), ("y", "<f8"), ("id", "<i8")])
+    images, tracks = [], [[] for _ in range(n_points)]
+    for k in range(n_images):
+        idx = A["ids"][A["offsets"][k]:A["offsets"][k + 1]]
+        n_free = 3 + k
+        p2d = np.zeros(len(idx) + n_free + (1 if k == 0 and len(idx) else 0), dtype=p2d_dtype)
+        p2d["x"][:len(idx)], p2d["y"][:len(idx)], p2d["id"][:len(idx)] = A["uv"][k][:, 0], A["uv"][k][:, 1], 5 + 3 * idx.astype(np.int64)
+        p2d["x"][len(idx):], p2d["y"][len(idx):], p2d["id"][len(idx):] = rng.uniform(0, W, len(p2d) - len(idx)), rng.uniform(0, H, len(p2d) - len(idx)), -1
+        if k == 0 and len(idx):
+            p2d[-1] = p2d[0]                                       # the same 3-D point observed twice
+        p2d = p2d[rng.permutation(len(p2d))]
+        for at, pid in enumerate(p2d["id"]):
+            if pid >= 0:
+                tracks[(int(pid) - 5) // 3].append((10 + 2 * k, at))
+        images.append({"id": 10 + 2 * k, "qvec": _rotmat_to_qvec(A["extrinsics"][k, :3, :3]), "tvec": A["extrinsics"][k, :3, 3].copy(),
+                       "camera_id": 3, "name": "view_%03d.%s" % (k, ext), "points2D": p2d})
+    order = rng.permutation(n_points)
+    points = {"ids": 5 + 3 * order.astype(np.int64), "xyz": A["points"][order], "rgb": rng.integers(0, 256, (n_points, 3)).astype(np.uint8),
+              "error": rng.uniform(0.1, 1.0, n_points), "tracks": [np.array(tracks[i], dtype=np.int32).reshape(-1, 2) for i in order]}
+    return {"cameras": cameras, "images": [images[i] for i in rng.permutation(n_images)], "points": points, "truth": A}
+
+
+def write_colmap_model(model, folder, binary=False):
+    """cameras / images / points3D of a colmap_model as .txt (numbers by repr: they read back to the same doubles) or .bin"""
+    import os
+    import struct
+    os.makedirs(folder, exist_ok=True)
+    model_ids = {"SIMPLE_PINHOLE": 0, "PINHOLE": 1, "SIMPLE_RADIAL": 2, "RADIAL": 3, "OPENCV": 4}
+    P = model["points"]
+    if binary:
+        with open(os.path.join(folder, "cameras.bin"), "wb") as f:
+            f.write(struct.pack("<Q", len(model["cameras"])))
+            for c in model["cameras"]:
+                f.write(struct.pack("<iiQQ", c["id"], model_ids[c["model"]], c["width"], c["height"]) + struct.pack("<%dd" % len(c["params"]), *c["params"]))
+        with open(os.path.join(folder, "images.bin"), "wb") as f:
+            f.write(struct.pack("<Q", len(model["images"])))
+            for im in model["images"]:
+                f.write(struct.pack("<i7di", im["id"], *im["qvec"], *im["tvec"], im["camera_id"]) + im["name"].encode() + b"\0")
+                f.write(struct.pack("<Q", len(im["points2D"])) + im["points2D"].tobytes())
+        with open(os.path.join(folder, "points3D.bin"), "wb") as f:
+            f.write(struct.pack("<Q", len(P["ids"])))
+            for i in range(len(P["ids"])):
+                f.write(struct.pack("<Q3d3BdQ", int(P["ids"][i]), *P["xyz"][i], *[int(v) for v in P["rgb"][i]], float(P["error"][i]), len(P["tracks"][i])))
+                f.write(P["tracks"][i].astype("<i4").tobytes())
+        return
+    with open(os.path.join(folder, "cameras.txt"), "w") as f:
+        f.write("# Camera list with one line of data per camera:\n#   CAMERA_ID, MODEL, WIDTH, HEIGHT, PARAMS[]\n")
+        for c in model["cameras"]:
+            f.write("%d %s %d %d %s\n" % (c["id"], c["model"], c["width"], c["height"], " ".join(repr(float(p)) for p in c["params"])))
+    with open(os.path.join(folder, "images.txt"), "w") as f:
+        f.write("# Image list with two lines of data per image:\n#   IMAGE_ID, QW, QX, QY, QZ, TX, TY, TZ, CAMERA_ID, NAME\n"
+                "#   POINTS2D[] as (X, Y, POINT3D_ID)\n")
+        for im in model["images"]:
+            f.write("%d %s %d %s\n" % (im["id"], " ".join(repr(float(v)) for v in list(im["qvec"]) + list(im["tvec"])), im["camera_id"], im["name"]))
+            f.write(" ".join("%r %r %d" % (float(p["x"]), float(p["y"]), int(p["id"])) for p in im["points2D"]) + "\n")
+    with open(os.path.join(folder, "points3D.txt"), "w") as f:
+        f.write("# 3D point list with one line of data per point:\n#   POINT3D_ID, X, Y, Z, R, G, B, ERROR, TRACK[] as (IMAGE_ID, POINT2D_IDX)\n")
+        for i in range(len(P["ids"])):
+            f.write("%d %s %d %d %d %r %s\n" % (int(P["ids"][i]), " ".join(repr(float(v)) for v in P["xyz"][i]), *[int(v) for v in P["rgb"][i]],
+                                               float(P["error"][i]), " ".join("%d %d" % (a, b) for a, b in P["tracks"][i])))
+
+
+def write_colmap_images(model, folder, seed=0):
+    """small random images under the names the model lists (the format follows the extension), at the camera's size"""
+    import os
+    from PIL import Image
+    os.makedirs(folder, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    cams = {c["id"]: c for c in model["cameras"]}
+    for im in model["images"]:
+        c = cams[im["camera_id"]]
+        Image.fromarray((255.0 * rng.random((c["height"], c["width"], 3))).astype(np.uint8)).save(os.path.join(folder, im["name"]))
