@@ -69,7 +69,9 @@ FAST = {
          "test_deconv2d_fuse_and_unet_pyramid_vs_reference_golden", "test_standalone_conv3d_block_trains_like_torch",
          "test_depthnet_on_its_own_vs_reference_golden", "test_execution_plans_follow_their_parameters"],
     GR: ["test_resize_planes", "test_gu_sampler_vs_oracle", "test_nerf_mlp_vs_oracle", "test_rendernet_forward_on_its_own_vs_reference_golden", "test_composite_vs_oracle",
-         "test_composite_backward_vs_fp64_autograd", "test_point_feats_backward_vs_fp64_grid_sample", "test_resize_planes_forward_backward_vs_fp64"],
+         "test_composite_backward_vs_fp64_autograd", "test_point_feats_backward_vs_fp64_grid_sample", "test_resize_planes_forward_backward_vs_fp64",
+         "test_gu_sampler_sizes_ties_and_zero_sigma", "test_gu_sampler_refusals", "test_point_feats_forward_volume_vs_fp64_grid_sample",
+         "test_point_feats_forward_images_vs_fp64", "test_composite_forward_regimes_vs_fp64"],
     GT: ["test_prob_depth_head_backward", "test_prob_conv_weight_gradient_marching_kernel", "test_conv3d_weight_gradient_cout8_paired_columns",
          "test_selective_weight_pack_matches_full_blob_and_is_checked", "test_packed_weight_reuse_follows_the_parameter_version", "test_pack_cache_follows_data_writes_of_a_legacy_optimizer_and_dies_with_its_parameter", "test_batchnorm_and_wgrad_scratch_survive_an_aborted_call",
          "test_fused_batchnorm_forms_equal_the_two_launch_forms", "test_weight_gradient_finish_permutes_and_clears",
@@ -77,7 +79,8 @@ FAST = {
          "test_conv_bn_block_with_padded_input_channels", "test_conv_plain_block_with_bias_one_plane",
          "test_conv_bn_block_two_segments_vs_two_batchnorm_calls"],
     GL: ["test_unsup_loss_multi_stage_matches_reference", "test_inverse_warping_matches_reference", "test_aug_loss_and_sl1_match_reference",
-         "test_unsup_loss_argument_checks"],
+         "test_unsup_loss_argument_checks", "test_inverse_warp_hostile_geometry_vs_fp64", "test_unsup_loss_terms_one_by_one_vs_fp64",
+         "test_masked_smooth_l1_vs_fp64"],
     GF: ["test_check_geometric_consistency_matches_reference", "test_filter_depth_matches_reference", "test_fuse_view_argument_checks",
          "test_filter_depth_tanks_matches_reference"],
     GD: ["test_tanks_loader_items_match_reference"],          # the DTU twin asserts `.is_cuda`; tests/test_dataset_cpu.py covers it

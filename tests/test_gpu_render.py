@@ -1,11 +1,13 @@
 """GPU parity tests of the rendering-consistency branch: every HIP
 kernel against the CPU oracle (oracle/render.py, oracle/conv3d.py) and against the fixtures captured
 from the reference's Rendering_Consistency_Net.forward with injected random draws."""
+import os
 import types
 
 import pytest
 import torch
 
+import loss_render_cases as LR
 from conftest import load_golden, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -458,3 +460,148 @@ def test_resize_planes_forward_backward_vs_fp64(hip, C, Cp, D, Do):
     n = Do if D == 1 else 2 * -(-(Do - 1) // (D - 1)) + 2
     gx = xg.grad.cpu().double()
     assert float((gx - xr.grad).abs().max()) <= n * (2 * D + n) * u * float(G[..., :C].abs().max())
+
+
+# ------------------------------------------------------------------------------------------------
+# forward kernels on hostile inputs against plain fp64 references (tests/loss_render_cases.py)
+# ------------------------------------------------------------------------------------------------
+def _emu_slow(flag):
+    if DEV == "cpu" and flag and os.environ.get("RCMVS_EMU_FULL", "0") != "1":
+        pytest.skip("slow on the kernel emulation: RCMVS_EMU_FULL=1 (always run on the GPU)")
+
+
+@pytest.mark.parametrize("N", LR.GU_N)
+@pytest.mark.parametrize("S", LR.GU_S)
+def test_gu_sampler_sizes_ties_and_zero_sigma(hip, S, N):
+    """rcmvs_gu_sample_fwd at S = 2, 3, below / at / above the power-of-two padding (64, 65, 127, 129, 1000), S > GU_THREADS up to the
+    4096 limit, two and six rays of a 5 x 7 image with the corners among the pixels, exact duplicates in eps, and (N = 6) one Gaussian
+    ray whose pseudo depth equals `near`: sigma == 0.  Gaussian rays: non-decreasing, and the multiset of z is, bit for bit, that of
+    mu + sigma * eps evaluated in fp32 in the kernel's operation order (it compiles with contraction off) -- nothing lost, duplicated
+    or replaced by the +inf padding.  Uniform rays: within the existing z tolerance of the fp64 samples, inside their strata (one ulp
+    of `far`, 2^-14, for the fp32 evaluation of lo + (hi - lo) u).  pts / ndc / dirs / rays_depth / target as in
+    test_gu_sampler_vs_oracle, pts and ndc against the fp64 projection of the sampler's own z."""
+    _emu_slow(S > 1000)
+    c = LR.gu_case(N, S)
+    r = LR.gu_reference(c)
+    z, pts, ndc, dirs, rdepth, target = (t.cpu() for t in hip.gu_sample(gpu(c["pseudo"]), gpu(c["img0"]), gpu(c["pix"].to(torch.int32)),
+                                                                        gpu(c["eps"]), gpu(c["u"]), gpu(c["cam"])))
+    half = N // 2
+    assert torch.equal(rdepth, r["rdepth"]) and torch.equal(target, r["target"])
+    assert bool(torch.isfinite(z).all())
+    assert bool((z[:half, 1:] >= z[:half, :-1]).all())
+    assert torch.equal(torch.sort(z[:half], dim=1).values, torch.sort(r["gauss32"][:half], dim=1).values)
+    if N >= 4:
+        assert bool((z[1] == c["near"]).all())                                                   # sigma == 0
+    assert float((z.double() - r["z64"]).abs().max()) < 2e-4
+    zu = z[half:].double()
+    assert bool((zu >= r["lo"] - 2.0 ** -14).all()) and bool((zu <= r["hi"] + 2.0 ** -14).all())
+    want_pts, want_ndc = LR.gu_points(c, r, z)
+    assert rel_err(dirs, r["dirs"]) < 1e-6
+    assert rel_err(pts, want_pts) < 1e-6
+    assert float((ndc.double() - want_ndc).abs().max()) < 2e-6
+
+
+def test_gu_sampler_refusals(hip):
+    from rc_mvsnet_amd import _lib
+    c = LR.gu_case(2, 3)
+    args = lambda N, S: (gpu(c["pseudo"]), gpu(c["img0"]), gpu(torch.zeros(2, N, dtype=torch.int32)), gpu(torch.zeros(N, S)),   # noqa: E731
+                         gpu(torch.zeros(max(N // 2, 1), S)), gpu(c["cam"]))
+    for N, S in ((3, 4), (2, 1), (2, 4097)):
+        with pytest.raises(_lib.RcmvsError):
+            hip.gu_sample(*args(N, S))
+
+
+def _point_feats_raw(hip, vol, imgs, poses, pts, ndc, nimg, ldf, sentinel):
+    """rcmvs_point_feats_fwd into a caller-owned, pre-filled feature matrix (ops.point_feats allocates its own)."""
+    from rc_mvsnet_amd import _lib
+    M = pts.shape[0]
+    feat = torch.full((M, ldf), sentinel, device=DEV)
+    Dv, hv, wv, _ = vol.shape
+    H, W = imgs.shape[-2:]
+    c = hip._chk
+    vol, imgs, poses, pts, ndc = (gpu(t) for t in (vol, imgs, poses, pts, ndc))           # named: the pointers must outlive the call
+    _lib.call("rcmvs_point_feats_fwd", c(vol, "volume"), c(imgs, "imgs"), c(poses, "poses"), c(pts, "pts"), c(ndc, "ndc"),
+              c(feat, "feat"), M, Dv, hv, wv, nimg, H, W, ldf, hip._stream())
+    return feat.cpu()
+
+
+@pytest.mark.parametrize("case", ["spread", "lattice", "Dv1", "hv1", "wv1", "collide"])
+def test_point_feats_forward_volume_vs_fp64_grid_sample(hip, case):
+    """Columns 0-7 of rcmvs_point_feats_fwd on the volumes of test_point_feats_backward_vs_fp64_grid_sample (an axis of size 1, points
+    on nodes / edges / far faces, M no multiple of 256) against fp64 F.grid_sample, no point excluded.  Bound: the fp32 coordinate
+    moves each axis weight by <= 4 u (n - 1), the eight products wx wy wz by <= 2 (dx + dy + dz) in sum, plus the roundings of the
+    products and of the eight additions: (24 (n - 1) + 16) u max|vol|, u = 2^-24, n the longest axis.  Rows far outside the volume
+    on every axis (1e9, +-1e30; on an axis of size 1 every finite coordinate is node 0, as in grid_sample) and rows with a NaN or an
+    infinite coordinate give exactly zero: zeros padding, and no tap of a NaN coordinate passes the bounds test."""
+    gen = torch.Generator().manual_seed(len(case))
+    Dv, hv, wv = {"spread": (7, 9, 13), "lattice": (5, 6, 7), "Dv1": (1, 9, 13), "hv1": (7, 1, 13), "wv1": (7, 9, 1), "collide": (2, 2, 2)}[case]
+    if case == "lattice":
+        ndc = _lattice_points(Dv, hv, wv, gen)
+    else:
+        ndc = -0.2 + 1.4 * torch.rand(1000 if case != "collide" else 5123, 3, generator=gen)
+    wild = torch.tensor([[1e9, 1e9, 1e9], [-1e30, -1e30, -1e30], [1e30, -1e30, 1e9], [float("nan"), 0.5, 0.5], [0.5, 0.5, float("nan")],
+                         [float("nan")] * 3, [0.5, float("inf"), 0.5]])
+    M0 = ndc.shape[0]
+    ndc = torch.cat((ndc, wild))
+    M = ndc.shape[0]
+    assert M % 256
+    vol = torch.randn(Dv, hv, wv, 8, generator=gen)
+    want, _ = _grid_sample_fp64(vol, ndc[:M0])
+    imgs, poses, _ = LR.point_image_case(1)
+    feat = _point_feats_raw(hip, vol, imgs, poses, torch.ones(M, 3), ndc, 0, 8, 7.0)
+    assert float(feat[M0:].abs().max()) == 0.0
+    u = 2.0 ** -24
+    err = float((feat[:M0].double() - want).abs().max())
+    bound = (24 * (max(Dv, hv, wv) - 1) + 16) * u * float(vol.abs().max())
+    print(f"point feats volume {case}: err {err:.3e} bound {bound:.3e}")
+    assert err <= bound
+
+
+@pytest.mark.parametrize("nimg", [0, 1, 3])
+@pytest.mark.parametrize("M", [1, 255, 257])
+def test_point_feats_forward_images_vs_fp64(hip, M, nimg):
+    """The image columns of rcmvs_point_feats_fwd (LR.point_image_case: 5 x 9 images, an identity pose with dyadic K and two small
+    rigid motions): points in front of every camera, behind them, with qz == 0 (+-inf, and NaN -> 0 as ATen's clip does) and
+    projections exactly on g = +-1, where the strict mask is decidable in both precisions.  Masks exact (the generic rows are shown
+    to keep |g| at least 1e-4 from 1), border-padded RGB at the existing 1e-5, ldf = 40 with every unused column left alone."""
+    imgs, poses, pts = LR.point_image_case(M)
+    rgb, mask, margin = LR.point_image_reference(imgs, poses, pts, nimg)
+    assert bool(((margin == 0.0) | (margin > 1e-4)).all())
+    vol = torch.randn(3, 4, 5, 8, generator=torch.Generator().manual_seed(1))
+    ndc = torch.rand(M, 3, generator=torch.Generator().manual_seed(2))
+    feat = _point_feats_raw(hip, vol, imgs, poses, pts, ndc, nimg, 40, -77.0)
+    assert bool((feat[:, 8 + 4 * nimg:] == -77.0).all())
+    assert bool(torch.isfinite(feat).all())
+    want_vol, _ = _grid_sample_fp64(vol, ndc)
+    assert float((feat[:, :8].double() - want_vol).abs().max()) < 1e-5 * float(want_vol.abs().max())
+    for i in range(nimg):
+        assert torch.equal(feat[:, 11 + 4 * i].double(), mask[:, i]), i
+        assert rel_err(feat[:, 8 + 4 * i:11 + 4 * i], rgb[:, i]) < 1e-5, i
+    if nimg and M > 1:
+        assert 0.0 < float(mask.mean()) < 1.0
+
+
+@pytest.mark.parametrize("N,S", [(1, 1), (63, 2), (65, 64), (70, 128), (5, 200), (3, 1000)])
+@pytest.mark.parametrize("regime", ["zero", "saturated", "mixed"])
+def test_composite_forward_regimes_vs_fp64(hip, N, S, regime):
+    """rcmvs_composite_fwd in the regimes of its backward test (alpha == 0 everywhere; alpha == 1.0f mid-ray, T at the 1e-10 floor behind
+    it; both mixed) and at its sizes: S < 64 (lanes that own no sample), S = 200, 1000 (no multiple of ceil(S / 64)).  Against the fp64
+    oracle; the yardstick is the same composition with fp32 ATen ops on the CPU (exp, exclusive cumprod): the kernel's error may be
+    twice the yardstick's plus one fp32 ulp of the value range (1 for alpha / weights / rgb, 1024 for the depth of z < 925).  Measured
+    on the MI355X, worst case (saturated, S = 64 and 128): weights err 1.6e-7 against a yardstick of 1.0e-7 to 1.2e-7."""
+    from oracle import render as orr
+    gen = torch.Generator().manual_seed(N * 7 + S)
+    raw, z = _composite_raw(N, S, regime, gen)
+    ref = orr.composite(raw.double(), z.double())
+    yard = orr.composite(raw, z)
+    rgb, depth, weights, alpha = (t.cpu() for t in hip.composite(gpu(raw), gpu(z)))
+    for name, got, key, ulp in (("alpha", alpha, "alpha", 2.0 ** -23), ("weights", weights, "weights", 2.0 ** -23), ("rgb", rgb, "rgb_map", 2.0 ** -23),
+                                ("depth", depth, "depth_map", 2.0 ** -13)):
+        assert bool(torch.isfinite(got).all()), name
+        e_k = float((got.double() - ref[key]).abs().max())
+        e_y = float((yard[key].double() - ref[key]).abs().max())
+        print(f"composite {regime} N={N} S={S} {name}: kernel {e_k:.3e} yardstick {e_y:.3e}")
+        assert e_k <= 2.0 * e_y + ulp, (name, e_k, e_y)
+    assert float(weights.double().sum(1).max()) <= 1.0 + S * 2.0 ** -23
+    if regime == "saturated":
+        assert float(alpha[:, S // 2].min()) == 1.0

@@ -168,3 +168,47 @@ def test_kernel_arithmetic_edge_cases(case_name, harness):
     if case_name == "a_view_that_sees_nothing":
         assert float(masks[1].sum()) == 0.0 and int(counts[1]) == 0
     assert int(counts.sum()) <= B * H * W
+
+
+def test_exclusion_caps_hold_for_the_fp64_references_alone():
+    """The hostile cases of tests/loss_render_cases.py, references only (no kernel): every knife-edge exclusion stays under the 1 % cap
+    that the GPU tests assert, the hand-built tables reach every class they claim (valid and masked pixels, pz < 0, pz == 0, positions
+    beyond 1e9, exact border positions), and the point-feature rows keep |g| either exactly on 1 or 1e-4 away from it."""
+    import loss_render_cases as LR
+    for H, W in LR.WARP_SHAPES:
+        seen = set()
+        for kind in LR.WARP_KINDS:
+            img, depth, coef = LR.hostile_warp_case(H, W, kind)
+            warped, mask, excluded = LR.hostile_warp_reference(H, W, kind)
+            x, y, pz = LR.warp_positions(coef, depth.double())
+            assert float(excluded.double().mean()) <= LR.CAP, (H, W, kind)
+            assert bool(torch.isfinite(warped).all()) and 0 < int(mask.sum()) < mask.numel()
+            assert not torch.equal(coef[0], coef[1])
+            seen |= {("x", v) for v in (-1, 0, W - 2, W - 1, W, -1 + 2.0 ** -20, -0.5, W - 0.5) if LR.dyadic(W) and bool((x == v).any())}
+            seen |= {("y", v) for v in (-1, 0, H - 2, H - 1, H, -1 + 2.0 ** -20, -0.5, H - 0.5) if bool((y == v).any())}
+            seen |= {c for c, hit in (("behind", pz < 0), ("zero", pz == 0), ("huge+", x > 1e9), ("huge-", x < -1e9)) if bool(hit.any())}
+        assert {"behind", "zero", "huge+", "huge-"} <= seen
+        for axis, n in (("x", W), ("y", H)):
+            if LR.dyadic(n):
+                assert {(axis, v) for v in (-1, 0, n - 2, n - 1, n, -1 + 2.0 ** -20, -0.5, n - 0.5)} <= seen, (H, W, axis, sorted(seen, key=str))
+    for name in LR.UNSUP_CASES:
+        R = LR.unsup_reference(name)
+        assert float(R["knife"].double().mean()) <= LR.CAP, name
+        assert int(R["knife"].sum()) == LR.KEEP_KNIFE.get(name, 0), name
+        hostile = name in LR.HOSTILE_LOSS
+        assert hostile or not bool((R["pz_bad"] | R["wild"]).any()), name
+        assert int((~(LR.dilate3(R["knife"] | R["pz_bad"]) | R["wild"])).sum()) >= R["knife"].numel() // 4, name    # what the gradient tests keep
+        assert not bool(R["tie"].any()), name
+        c = LR.unsup_case(name)
+        if c["blind"]:
+            assert float(R["masks"][-1].sum()) == 0.0
+        if c["srcs"].shape[1] > 1:
+            assert not torch.equal(c["coef64"][:, 0], c["coef64"][:, 1])
+    assert bool(LR.unsup_reference("hostile_zero")["pz_bad"].any()) and bool(LR.unsup_reference("hostile_huge")["wild"].any())
+    assert bool((LR.unsup_case("hostile_behind")["depth"] < 0).any())
+    for M in (1, 255, 257):
+        imgs, poses, pts = LR.point_image_case(M)
+        rgb, mask, margin = LR.point_image_reference(imgs, poses, pts, 3)
+        assert bool(((margin == 0.0) | (margin > 1e-4)).all()) and bool(torch.isfinite(rgb).all())
+        if M > 1:
+            assert bool((margin[:, 0] == 0.0).any()) and bool((pts[:, 2] < 0).any()) and bool((pts[:, 2] == 0).any())
