@@ -10,12 +10,22 @@
 3. ``depth_ranges``: per image the exact order statistics of its points' depths at the ranks ``int(c * 0.01)`` and
    ``int(c * 0.99)`` -> ``depth_min``, ``depth_max``; ``depth_interval = (depth_max - depth_min) / (max_d - 1) / interval_scale``.
 
-Limits: ``SIMPLE_PINHOLE`` / ``PINHOLE`` cameras only (no undistortion), intrinsics are written as COLMAP states them (no
-half-pixel shift).  CUDA tensors only; no CPU fallback.
+With ``--undistort`` the polynomial (Brown) camera models ``SIMPLE_RADIAL``, ``RADIAL``, ``OPENCV`` and ``FULL_OPENCV`` are read
+too, and every image with a non-zero coefficient (every image, when ``--focal-scale`` is not 1) is resampled on the GPU
+(``undistort_image``: csrc/undistort.hip, arithmetic in csrc/undistort_math.h, restated by tests/undistort_oracle.py) to the
+pinhole camera (s fx, s fy, cx, cy) of the same size, s = ``--focal-scale``: pixel centres at +0.5 as in COLMAP, bilinear with the
+border pixel repeated, an output pixel whose source position is not inside the image is black and counted (``blank_fraction_max``
+in the summary).  The undistorted image is saved as JPEG at quality 95; the other images are copied as before.
 
-    python -m rc_mvsnet_amd.colmap_import --model SPARSE --images DIR --out TESTPATH/SCENE
+Limits: without ``--undistort`` ``SIMPLE_PINHOLE`` / ``PINHOLE`` cameras only; intrinsics are written as COLMAP states them (no
+half-pixel shift).  The output camera is not chosen automatically (COLMAP's ``blank_pixels`` / ``min_scale`` search is not
+implemented): pick ``--focal-scale`` and read ``blank_fraction_max``.  Very strong barrel distortion folds over far outside the
+calibrated radius, as it does in COLMAP.  The fisheye models and ``FOV`` are refused.  CUDA tensors only; no CPU fallback.
+
+    python -m rc_mvsnet_amd.colmap_import --model SPARSE --images DIR --out TESTPATH/SCENE [--undistort [--focal-scale S]]
 """
 import argparse
+import ctypes
 import json
 import math
 import os
@@ -98,6 +108,31 @@ def rank_pair(c):
     return int(c * 0.01), int(c * 0.99)
 
 
+def undistort_image(img, camera, dist, focal_scale=1.0):
+    """img (H,W,3) uint8 of the camera (fx, fy, cx, cy) with distortion dist = (k1, k2, p1, p2, k3, k4, k5, k6) -> (out (H,W,3) uint8
+    as seen by the pinhole camera (s fx, s fy, cx, cy), s = focal_scale; blank = the number of output pixels without a source,
+    written (0, 0, 0)).  Two runs give the same bytes."""
+    if img.dim() != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise _lib.RcmvsError(f"undistort_image: expected an (H,W,3) image, got {tuple(img.shape)}")
+    H, W = int(img.shape[0]), int(img.shape[1])
+    if H * W * 3 >= 1 << 31:
+        raise _lib.RcmvsError(f"undistort_image: {H} x {W} x 3 bytes (below 2^31)")
+    camera, dist = [float(v) for v in camera], [float(v) for v in dist]
+    if len(camera) != 4 or len(dist) != 8:
+        raise _lib.RcmvsError(f"undistort_image: expected camera (fx, fy, cx, cy) and 8 coefficients, got {len(camera)} and {len(dist)} numbers")
+    if not all(math.isfinite(v) for v in camera + dist) or not (camera[0] > 0 and camera[1] > 0):
+        raise _lib.RcmvsError(f"undistort_image: camera {camera}, coefficients {dist} (finite, focal lengths positive)")
+    if not (math.isfinite(focal_scale) and focal_scale > 0):
+        raise _lib.RcmvsError(f"undistort_image: focal_scale {focal_scale} (finite, positive)")
+    fx, fy, cx, cy = camera
+    src = _chk(img, "img", torch.uint8)
+    out = torch.empty_like(img)
+    blank = torch.empty(1, device=img.device, dtype=torch.int32)
+    _lib.call("rcmvs_undistort_rgb8", src, _chk(out, "out", torch.uint8), H, W, fx, fy, cx, cy, float(focal_scale) * fx, float(focal_scale) * fy,
+              (ctypes.c_double * 8)(*dist), _chk(blank, "blank", torch.int32), _stream())
+    return out, int(blank.item())
+
+
 # ---- files ------------------------------------------------------------------------------------------------------------
 def write_pair_file(filename, lists):
     """lists: [(ref, [(src, score), ...])] of the images that have partners.  The first line counts the entries that follow (it is
@@ -124,14 +159,35 @@ def _copy_image(src, dst, size):
         shutil.copyfile(src, dst)                                 # byte for byte
 
 
-def import_scene(model, images, out, max_d=192, interval_scale=1.0, num_src=10, theta0=5.0, sigma1=1.0, sigma2=10.0, device="cuda:0"):
-    """COLMAP sparse model folder + image folder -> the scan folder ``out``; returns the summary dict the command line prints."""
+def _undistort_file(src, dst, size, K, dist, focal_scale, dev):
+    """decode, check the size against the camera, resample on the device, save as JPEG at quality 95 -> blank pixel count"""
+    from PIL import Image
+    try:
+        with Image.open(src) as im:
+            if im.size != size:
+                raise _lib.RcmvsError(f"{src}: size {im.size[0]} x {im.size[1]} differs from its camera's {size[0]} x {size[1]}")
+            rgb = np.array(im.convert("RGB"), dtype=np.uint8)
+    except OSError as e:
+        raise _lib.RcmvsError(f"{src}: not a readable image ({e})") from None
+    got, blank = undistort_image(torch.from_numpy(rgb).to(dev), (K[0, 0], K[1, 1], K[0, 2], K[1, 2]), dist, focal_scale)
+    Image.fromarray(got.cpu().numpy()).save(dst, format="JPEG", quality=95)
+    return blank
+
+
+def import_scene(model, images, out, max_d=192, interval_scale=1.0, num_src=10, theta0=5.0, sigma1=1.0, sigma2=10.0, device="cuda:0",
+                 undistort=False, focal_scale=1.0):
+    """COLMAP sparse model folder + image folder -> the scan folder ``out``; returns the summary dict the command line prints.
+    ``undistort``: read the polynomial camera models too and resample their images to the pinhole camera (focal_scale fx,
+    focal_scale fy, cx, cy), which is what ``cams/`` then states."""
     max_d, num_src = int(max_d), int(num_src)
     if max_d < 2 or not (interval_scale > 0 and math.isfinite(interval_scale)):
         raise _lib.RcmvsError(f"import_scene: max_d {max_d} (at least 2), interval_scale {interval_scale} (positive)")
     if not 1 <= num_src <= MAX_SRC:
         raise _lib.RcmvsError(f"import_scene: num_src {num_src} (1 .. {MAX_SRC}, RCMVS_VS_MAX_SRC)")
-    M = colmap_io.read_model(model) if isinstance(model, (str, os.PathLike)) else model
+    focal_scale = float(focal_scale)
+    if not (math.isfinite(focal_scale) and focal_scale > 0) or (focal_scale != 1.0 and not undistort):
+        raise _lib.RcmvsError(f"import_scene: focal_scale {focal_scale} (finite, positive; another value than 1 needs undistort=True)")
+    M = colmap_io.read_model(model, distortion=bool(undistort)) if isinstance(model, (str, os.PathLike)) else model
     n, names = len(M["image_ids"]), M["names"]
     if n == 0 or len(M["points"]) == 0:
         raise _lib.RcmvsError(f"{M['files']['images']}: {n} images and {len(M['points'])} points: nothing to import")
@@ -153,7 +209,8 @@ def import_scene(model, images, out, max_d=192, interval_scale=1.0, num_src=10, 
     top_ids, top_scores, positive = (t.cpu().numpy() for t in top_views(scores, k_src))
     for sub in ("images", "cams"):
         os.makedirs(os.path.join(out, sub), exist_ok=True)
-    lists, skipped = [], []
+    lists, skipped, undistorted, blank_max = [], [], 0, 0.0
+    dist = M.get("distortion") if undistort else None
     for k in range(n):
         listed = min(int(positive[k]), k_src)
         if listed == 0:
@@ -162,15 +219,25 @@ def import_scene(model, images, out, max_d=192, interval_scale=1.0, num_src=10, 
             lists.append((k, [(int(top_ids[k, r]), float(top_scores[k, r])) for r in range(listed)]))
         cam = np.zeros((2, 4, 4), dtype=np.float64)
         cam[0], cam[1, :3, :3] = M["extrinsics"][k], M["intrinsics"][k]
+        cam[1, 0, 0], cam[1, 1, 1] = focal_scale * cam[1, 0, 0], focal_scale * cam[1, 1, 1]
         interval = (dr[k, 1] - dr[k, 0]) / (max_d - 1) / interval_scale
         cam[1, 3] = (dr[k, 0], interval, max_d, dr[k, 1])
         scan_io.write_cam(os.path.join(out, "cams", "%08d_cam.txt" % k), cam)
-        _copy_image(os.path.join(images, names[k]), os.path.join(out, "images", "%08d.jpg" % k), (int(M["sizes"][k, 0]), int(M["sizes"][k, 1])))
+        src, dst, size = os.path.join(images, names[k]), os.path.join(out, "images", "%08d.jpg" % k), (int(M["sizes"][k, 0]), int(M["sizes"][k, 1]))
+        if undistort and (focal_scale != 1.0 or (dist is not None and bool(np.any(dist[k] != 0)))):
+            row = dist[k] if dist is not None else np.zeros(8)
+            blank = _undistort_file(src, dst, size, M["intrinsics"][k], row, focal_scale, dev)
+            undistorted, blank_max = undistorted + 1, max(blank_max, blank / (size[0] * size[1]))
+        else:
+            _copy_image(src, dst, size)
     write_pair_file(os.path.join(out, "pair.txt"), lists)
-    return {"scene": os.fspath(out), "images": n, "points": int(len(M["points"])), "observations": int(len(M["ids"])), "num_src": num_src,
-            "max_d": max_d, "interval_scale": float(interval_scale), "refs": len(lists), "skipped_refs": skipped,
-            "depth_min": float(dr[:, 0].min()), "depth_max": float(dr[:, 1].max()),
-            "image_names": {"%08d" % k: names[k] for k in range(n)}}
+    summary = {"scene": os.fspath(out), "images": n, "points": int(len(M["points"])), "observations": int(len(M["ids"])), "num_src": num_src,
+               "max_d": max_d, "interval_scale": float(interval_scale), "refs": len(lists), "skipped_refs": skipped,
+               "depth_min": float(dr[:, 0].min()), "depth_max": float(dr[:, 1].max()),
+               "image_names": {"%08d" % k: names[k] for k in range(n)}}
+    if undistort:
+        summary.update(undistorted=undistorted, focal_scale=focal_scale, blank_fraction_max=float(blank_max))
+    return summary
 
 
 def parse_args(argv=None):
@@ -184,7 +251,16 @@ def parse_args(argv=None):
     ap.add_argument("--theta0", type=float, default=5.0)
     ap.add_argument("--sigma1", type=float, default=1.0)
     ap.add_argument("--sigma2", type=float, default=10.0)
-    return ap.parse_args(argv)
+    ap.add_argument("--undistort", action="store_true", help="read SIMPLE_RADIAL / RADIAL / OPENCV / FULL_OPENCV cameras too and resample their images "
+                    "to the pinhole camera of the same principal point and size (GPU)")
+    ap.add_argument("--focal-scale", type=float, default=None, metavar="S", help="with --undistort: the output focal lengths are S times the camera's "
+                    "(default 1; below 1 keeps more of the field of view, above 1 crops blank borders away: read blank_fraction_max)")
+    args = ap.parse_args(argv)
+    if args.focal_scale is not None and not args.undistort:
+        ap.error("--focal-scale needs --undistort")
+    if args.focal_scale is None:
+        args.focal_scale = 1.0
+    return args
 
 
 def main(argv=None):
@@ -193,7 +269,7 @@ def main(argv=None):
         raise SystemExit("colmap_import: needs a GPU (view selection and depth ranges have no CPU fallback)")
     _lib.load()
     summary = import_scene(args.model, args.images, args.out, max_d=args.max_d, interval_scale=args.interval_scale, num_src=args.num_src,
-                           theta0=args.theta0, sigma1=args.sigma1, sigma2=args.sigma2)
+                           theta0=args.theta0, sigma1=args.sigma1, sigma2=args.sigma2, undistort=args.undistort, focal_scale=args.focal_scale)
     print(json.dumps(summary), flush=True)
     return summary
 

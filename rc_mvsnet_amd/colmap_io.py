@@ -4,9 +4,13 @@
 id, points renumbered 0..m-1 in ascending point id, and per image an ascending duplicate-free list of point indices as CSR
 (``offsets`` (n+1) int64, ``ids`` int32).  World-to-camera is ``x_cam = R(q) x_w + t`` with q = (w, x, y, z).
 
-Only ``SIMPLE_PINHOLE`` (f, cx, cy) and ``PINHOLE`` (fx, fy, cx, cy) cameras are accepted: images with any other model must be
-undistorted first (COLMAP's image_undistorter), which is out of scope here.  A truncated or malformed file, a non-finite number,
-an image whose camera is unknown and an observation of an unknown point raise ``RcmvsError`` naming the file and the record.
+By default only ``SIMPLE_PINHOLE`` (f, cx, cy) and ``PINHOLE`` (fx, fy, cx, cy) cameras are accepted: images with any other model
+must be undistorted first.  With ``distortion=True`` the readers also accept the polynomial (Brown) models ``SIMPLE_RADIAL``
+(f, cx, cy, k), ``RADIAL`` (f, cx, cy, k1, k2), ``OPENCV`` (fx, fy, cx, cy, k1, k2, p1, p2) and ``FULL_OPENCV`` (... k3, k4, k5, k6),
+and the model carries ``distortion`` (n, 8) fp64 in the fixed order k1, k2, p1, p2, k3, k4, k5, k6 (zeros where a model has no such
+term) and ``models`` [n]; ``colmap_import.import_scene(undistort=True)`` resamples such images on the GPU.  The fisheye models and
+``FOV`` are refused in both modes.  A truncated or malformed file, a non-finite number, an image whose camera is unknown and an
+observation of an unknown point raise ``RcmvsError`` naming the file and the record.
 """
 import os
 import struct
@@ -17,14 +21,24 @@ from ._lib import RcmvsError
 
 # name -> (binary model id, number of parameters)
 CAMERA_MODELS = {"SIMPLE_PINHOLE": (0, 3), "PINHOLE": (1, 4)}
+# the polynomial (Brown) models the readers accept with distortion=True
+DISTORTED_MODELS = {"SIMPLE_RADIAL": (2, 4), "RADIAL": (3, 5), "OPENCV": (4, 8), "FULL_OPENCV": (6, 12)}
 _MODEL_NAMES = {0: "SIMPLE_PINHOLE", 1: "PINHOLE", 2: "SIMPLE_RADIAL", 3: "RADIAL", 4: "OPENCV", 5: "OPENCV_FISHEYE", 6: "FULL_OPENCV",
                 7: "FOV", 8: "SIMPLE_RADIAL_FISHEYE", 9: "RADIAL_FISHEYE", 10: "THIN_PRISM_FISHEYE"}
 _POINT2D = np.dtype([("x", "<f8"), ("y", "<f8"), ("id", "<i8")])
 
 
-def _model_error(path, what, model):
+def _model_error(path, what, model, distortion=False):
+    if distortion:
+        return RcmvsError(f"{path}: {what}: camera model {model} is not supported (SIMPLE_PINHOLE, PINHOLE, {', '.join(DISTORTED_MODELS)}): "
+                          "fisheye and FOV images must be undistorted first")
     return RcmvsError(f"{path}: {what}: camera model {model} is not supported (SIMPLE_PINHOLE and PINHOLE only): "
-                      "the images must be undistorted first")
+                      "the images must be undistorted first" +
+                      (" (colmap_import --undistort does it for this model)" if model in DISTORTED_MODELS else ""))
+
+
+def _models(distortion):
+    return dict(CAMERA_MODELS, **DISTORTED_MODELS) if distortion else CAMERA_MODELS
 
 
 def _finite(path, what, values):
@@ -83,18 +97,19 @@ class _Bin:
 
 
 # ---- cameras ----------------------------------------------------------------------------------------------------------
-def _camera(path, what, cid, model, w, h, params):
-    if model not in CAMERA_MODELS:
-        raise _model_error(path, what, model)
-    if len(params) != CAMERA_MODELS[model][1]:
-        raise RcmvsError(f"{path}: {what}: {model} takes {CAMERA_MODELS[model][1]} parameters, found {len(params)}")
+def _camera(path, what, cid, model, w, h, params, distortion=False):
+    models = _models(distortion)
+    if model not in models:
+        raise _model_error(path, what, model, distortion)
+    if len(params) != models[model][1]:
+        raise RcmvsError(f"{path}: {what}: {model} takes {models[model][1]} parameters, found {len(params)}")
     _finite(path, what, params)
     if w <= 0 or h <= 0:
         raise RcmvsError(f"{path}: {what}: size {w} x {h}")
     return {"id": int(cid), "model": model, "width": int(w), "height": int(h), "params": np.array(params, dtype=np.float64)}
 
 
-def read_cameras_text(path):
+def read_cameras_text(path, distortion=False):
     cams = {}
     for no, ln in _text_records(path):
         if not ln.strip():
@@ -104,21 +119,21 @@ def read_cameras_text(path):
             cid, model, w, h, params = int(t[0]), t[1], int(t[2]), int(t[3]), [float(v) for v in t[4:]]
         except (ValueError, IndexError):
             raise RcmvsError(f"{path}: {what}: expected `id model width height params...`") from None
-        cams[cid] = _camera(path, f"{what} (camera {cid})", cid, model, w, h, params)
+        cams[cid] = _camera(path, f"{what} (camera {cid})", cid, model, w, h, params, distortion)
     return cams
 
 
-def read_cameras_binary(path):
-    b, cams = _Bin(path), {}
+def read_cameras_binary(path, distortion=False):
+    b, cams, models = _Bin(path), {}, _models(distortion)
     (n,) = b.take("<Q", "camera count")
     for k in range(n):
         what = f"camera record {k}"
         cid, mid, w, h = b.take("<iiQQ", what)
         name = _MODEL_NAMES.get(mid, f"id {mid}")
-        if name not in CAMERA_MODELS:
-            raise _model_error(path, f"{what} (camera {cid})", name)
-        params = b.take("<%dd" % CAMERA_MODELS[name][1], what)
-        cams[cid] = _camera(path, f"{what} (camera {cid})", cid, name, w, h, params)
+        if name not in models:
+            raise _model_error(path, f"{what} (camera {cid})", name, distortion)
+        params = b.take("<%dd" % models[name][1], what)
+        cams[cid] = _camera(path, f"{what} (camera {cid})", cid, name, w, h, params, distortion)
     b.done()
     return cams
 
@@ -238,11 +253,26 @@ def camera_centre(R, t):
     return -(np.asarray(R, dtype=np.float64).T @ np.asarray(t, dtype=np.float64))
 
 
+_ONE_FOCAL = ("SIMPLE_PINHOLE", "SIMPLE_RADIAL", "RADIAL")
+
+
 def intrinsic_matrix(cam):
-    """K of a SIMPLE_PINHOLE / PINHOLE camera, parameters unchanged (no half-pixel shift)"""
+    """K of a camera (the pinhole part of a distorted model), parameters unchanged (no half-pixel shift)"""
     p = cam["params"]
-    fx, fy, cx, cy = (p[0], p[0], p[1], p[2]) if cam["model"] == "SIMPLE_PINHOLE" else (p[0], p[1], p[2], p[3])
+    fx, fy, cx, cy = (p[0], p[0], p[1], p[2]) if cam["model"] in _ONE_FOCAL else (p[0], p[1], p[2], p[3])
     return np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
+
+
+def distortion_row(cam):
+    """(8,) fp64 in the fixed order k1, k2, p1, p2, k3, k4, k5, k6; zeros where the camera's model has no such term"""
+    p, d = cam["params"], np.zeros(8)
+    if cam["model"] == "SIMPLE_RADIAL":
+        d[0] = p[3]
+    elif cam["model"] == "RADIAL":
+        d[:2] = p[3:5]
+    elif cam["model"] in ("OPENCV", "FULL_OPENCV"):
+        d[:len(p) - 4] = p[4:]
+    return d
 
 
 def _pick(folder, stem):
@@ -253,12 +283,13 @@ def _pick(folder, stem):
     raise RcmvsError(f"{folder}: neither {stem}.txt nor {stem}.bin")
 
 
-def read_model(folder):
+def read_model(folder, distortion=False):
     """-> dict: image_ids (n,) int64 ascending, names [n], camera_ids (n,), qvec (n,4), tvec (n,3), extrinsics (n,4,4), centres (n,3),
     intrinsics (n,3,3), sizes (n,2) int64 as (width, height), point_ids (m,) int64 ascending, points (m,3), offsets (n+1,) int64,
-    ids int32, files {cameras, images, points3D}."""
+    ids int32, files {cameras, images, points3D}.  With ``distortion=True`` the polynomial camera models are read too, and the dict
+    also has distortion (n,8) fp64 as k1, k2, p1, p2, k3, k4, k5, k6 and models [n]."""
     (pc, bc), (pi, bi), (pp, bp) = _pick(folder, "cameras"), _pick(folder, "images"), _pick(folder, "points3D")
-    cams = (read_cameras_binary if bc else read_cameras_text)(pc)
+    cams = (read_cameras_binary if bc else read_cameras_text)(pc, distortion)
     imgs = (read_images_binary if bi else read_images_text)(pi)
     pids, xyz = (read_points3d_binary if bp else read_points3d_text)(pp)
     order = np.argsort(pids, kind="stable")
@@ -272,6 +303,7 @@ def read_model(folder):
             raise RcmvsError(f"{pi}: image {a['id']} is listed twice")
     E, C, K = np.zeros((n, 4, 4)), np.zeros((n, 3)), np.zeros((n, 3, 3))
     sizes, offsets, lists = np.zeros((n, 2), dtype=np.int64), np.zeros(n + 1, dtype=np.int64), []
+    D, models = np.zeros((n, 8)), []
     for k, im in enumerate(imgs):
         if im["camera_id"] not in cams:
             raise RcmvsError(f"{pi}: image {im['id']} ({im['name']}): unknown camera id {im['camera_id']}")
@@ -282,6 +314,8 @@ def read_model(folder):
             raise RcmvsError(f"{pi}: image {im['id']} ({im['name']}): zero quaternion") from None
         E[k, :3, :3], E[k, :3, 3], E[k, 3, 3] = R, im["tvec"], 1.0
         C[k], K[k], sizes[k] = camera_centre(R, im["tvec"]), intrinsic_matrix(cam), (cam["width"], cam["height"])
+        D[k] = distortion_row(cam)
+        models.append(cam["model"])
         seen = im["points2D"]["id"]
         seen = np.unique(seen[seen != -1])
         at = np.searchsorted(pids, seen)
@@ -290,10 +324,13 @@ def read_model(folder):
             raise RcmvsError(f"{pi}: image {im['id']} ({im['name']}): observation of unknown point {int(seen[bad][0])}")
         lists.append(at.astype(np.int32))
         offsets[k + 1] = offsets[k] + len(at)
-    return {"image_ids": np.array([im["id"] for im in imgs], dtype=np.int64), "names": [im["name"] for im in imgs],
-            "camera_ids": np.array([im["camera_id"] for im in imgs], dtype=np.int64),
-            "qvec": np.array([im["qvec"] for im in imgs], dtype=np.float64).reshape(n, 4),
-            "tvec": np.array([im["tvec"] for im in imgs], dtype=np.float64).reshape(n, 3),
-            "extrinsics": E, "centres": C, "intrinsics": K, "sizes": sizes, "point_ids": pids, "points": xyz, "offsets": offsets,
-            "ids": np.concatenate(lists).astype(np.int32) if lists else np.zeros(0, dtype=np.int32),
-            "files": {"cameras": pc, "images": pi, "points3D": pp}}
+    M = {"image_ids": np.array([im["id"] for im in imgs], dtype=np.int64), "names": [im["name"] for im in imgs],
+         "camera_ids": np.array([im["camera_id"] for im in imgs], dtype=np.int64),
+         "qvec": np.array([im["qvec"] for im in imgs], dtype=np.float64).reshape(n, 4),
+         "tvec": np.array([im["tvec"] for im in imgs], dtype=np.float64).reshape(n, 3),
+         "extrinsics": E, "centres": C, "intrinsics": K, "sizes": sizes, "point_ids": pids, "points": xyz, "offsets": offsets,
+         "ids": np.concatenate(lists).astype(np.int32) if lists else np.zeros(0, dtype=np.int32),
+         "files": {"cameras": pc, "images": pi, "points3D": pp}}
+    if distortion:
+        M["distortion"], M["models"] = D, models
+    return M

@@ -618,19 +618,33 @@ def colmap_arrays(n_images=6, n_points=400, hw=(64, 96), seed=0, radius=4.0, ext
             "ids": np.concatenate(lists).astype(np.int32), "uv": uvs, "hw": (H, W)}
 
 
-def colmap_model(n_images=6, n_points=400, hw=(64, 96), seed=0, camera_model="PINHOLE", ext="jpg", **kwargs):
+# moderate barrel distortion in each polynomial model's own parameter order (after the focal lengths and the principal point)
+COLMAP_DISTORTION = {"SIMPLE_RADIAL": [-0.12], "RADIAL": [-0.12, 0.03], "OPENCV": [-0.12, 0.03, 0.004, -0.003],
+                     "FULL_OPENCV": [-0.12, 0.03, 0.004, -0.003, 0.01, 0.02, -0.01, 0.005]}
+
+
+def colmap_model(n_images=6, n_points=400, hw=(64, 96), seed=0, camera_model="PINHOLE", ext="jpg", distortion=None, **kwargs):
     """colmap_arrays as COLMAP's records, with what a reader has to cope with: image ids 10, 12, ... listed in shuffled order, point
     ids 5, 8, ... listed in shuffled order, 2-D points in shuffled order with unmatched ones (point3D_id -1) and one observation
-    listed twice.  -> dict(cameras, images, points, truth=the colmap_arrays dict in renumbered order)."""
+    listed twice.  -> dict(cameras, images, points, truth=the colmap_arrays dict in renumbered order).  ``camera_model`` may be a
+    polynomial model (SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV) with ``distortion`` = its coefficients in its own order (default
+    COLMAP_DISTORTION); the 2-D points stay the pinhole projections, which the import does not read."""
     A = colmap_arrays(n_images, n_points, hw, seed, **kwargs)
     rng = np.random.default_rng(seed + 7)
     H, W = hw
     K = A["intrinsics"][0]
-    if camera_model == "SIMPLE_PINHOLE":
+    if camera_model in ("SIMPLE_PINHOLE", "SIMPLE_RADIAL", "RADIAL"):
         A["intrinsics"][:, 1, 1] = K[0, 0]
         params = [K[0, 0], K[0, 2], K[1, 2]]
     else:
         params = [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]
+    if camera_model in COLMAP_DISTORTION:
+        coeffs = list(COLMAP_DISTORTION[camera_model] if distortion is None else distortion)
+        if len(coeffs) != len(COLMAP_DISTORTION[camera_model]):
+            raise ValueError(f"{camera_model} takes {len(COLMAP_DISTORTION[camera_model])} distortion coefficients, got {len(coeffs)}")
+        params = params + coeffs
+    elif distortion is not None:
+        raise ValueError(f"{camera_model} has no distortion coefficients")
     cameras = [{"id": 3, "model": camera_model, "width": W, "height": H, "params": [float(p) for p in params]}]
     p2d_dtype = np.dtype([("x", "<f8"), ("y", "<f8"), ("id", "<i8")])
     images, tracks = [], [[] for _ in range(n_points)]
@@ -659,7 +673,7 @@ def write_colmap_model(model, folder, binary=False):
     import os
     import struct
     os.makedirs(folder, exist_ok=True)
-    model_ids = {"SIMPLE_PINHOLE": 0, "PINHOLE": 1, "SIMPLE_RADIAL": 2, "RADIAL": 3, "OPENCV": 4}
+    model_ids = {"SIMPLE_PINHOLE": 0, "PINHOLE": 1, "SIMPLE_RADIAL": 2, "RADIAL": 3, "OPENCV": 4, "OPENCV_FISHEYE": 5, "FULL_OPENCV": 6}
     P = model["points"]
     if binary:
         with open(os.path.join(folder, "cameras.bin"), "wb") as f:

@@ -5,9 +5,18 @@ three phases (pair scores, top views, depth ranks) are timed with device events 
 warm-up.  The yardstick is the numpy oracle (tests/colmap_oracle.py) on the same model and the same host, timed once; the results
 of both are compared.  ``--rocprof DIR`` also runs the three phases once in a child process under ``rocprofv3 --kernel-trace --stats``.
 
-    python tools/colmap_import_bench.py [--reps 5] [--rocprof DIR] [--no-cpu-baseline] [--out profiles/colmap_import_bench.json]
+The undistortion phase (``undistort_image``'s launch, csrc/undistort.hip) runs on OPENCV images of 1080 x 1920 and 3000 x 4000 (both
+ASSUMED sizes): the kernel alone from its own start / stop timestamps (rcmvs_undistort_rgb8_timed), median of --reps launches
+after a warm-up; against the numpy oracle (tests/undistort_oracle.py) on the same host, whose bytes and
+blank count are compared, and against the bytes-moved floor: 3 H W bytes read plus 3 H W written at 8 TB/s.  ``host_codec_ms`` is
+what the import spends around the launch on the same host: PIL decoding a quality-95 JPEG of that size (a smooth image with mild
+noise) and encoding the result, median of 3.
+
+    python tools/colmap_import_bench.py [--reps 5] [--phases all|import|undistort] [--rocprof DIR] [--no-cpu-baseline]
+                                        [--out profiles/colmap_import_bench.json]
 """
 import argparse
+import ctypes
 import json
 import os
 import subprocess
@@ -39,9 +48,77 @@ def event_ms(fn, reps):
     return out, round(float(np.median(times)), 4)
 
 
+UNDISTORT_SIZES, HBM_BYTES_PER_S = ((1080, 1920), (3000, 4000)), 8e12
+
+
+def host_codec_ms(h, w):
+    """-> (decode ms, encode ms) of a quality-95 JPEG of a smooth h x w image with mild noise, PIL, median of 3"""
+    import io
+    from PIL import Image
+    ys, xs = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    rgb = np.stack([128 + 100 * np.sin(xs / 97.0), 128 + 100 * np.cos(ys / 61.0), 128 + 90 * np.sin((xs + ys) / 143.0)], 2)
+    rgb = np.clip(rgb + np.random.default_rng(0).normal(0.0, 4.0, rgb.shape), 0, 255).astype(np.uint8)
+    dec, enc = [], []
+    for _ in range(3):
+        buf = io.BytesIO()
+        t0 = time.perf_counter()
+        Image.fromarray(rgb).save(buf, format="JPEG", quality=95)
+        t1 = time.perf_counter()
+        with Image.open(io.BytesIO(buf.getvalue())) as im:
+            np.array(im.convert("RGB"), dtype=np.uint8)
+        t2 = time.perf_counter()
+        enc.append((t1 - t0) * 1e3)
+        dec.append((t2 - t1) * 1e3)
+    return round(float(np.median(dec)), 1), round(float(np.median(enc)), 1)
+
+
+def undistort_phase(reps, cpu_baseline, dev="cuda:0"):
+    """-> the "undistort" entry of the JSON line: one dict per image size"""
+    from rc_mvsnet_amd.ops import _chk, _stream
+    rows = []
+    for h, w in UNDISTORT_SIZES:
+        img = np.random.default_rng(5).integers(0, 256, (h, w, 3), dtype=np.uint8)
+        cam, dist = (1.1 * w, 1.09 * w, 0.5 * w - 7.3, 0.5 * h + 4.6), (0.09, 0.02, 0.001, -0.0015, 0.0, 0.0, 0.0, 0.0)
+        src = torch.from_numpy(img).to(dev)
+        out, blank = torch.empty_like(src), torch.empty(1, device=dev, dtype=torch.int32)
+        d8 = (ctypes.c_double * 8)(*dist)
+
+        events = []
+        for i in range(reps + 1):                                                 # the first launch is the warm-up
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[0].record()
+            ev[1].record()                                                        # a torch event owns its hipEvent_t after a first record
+            _lib.call("rcmvs_undistort_rgb8_timed", _chk(src, "src", torch.uint8), _chk(out, "out", torch.uint8), h, w, *cam, cam[0], cam[1], d8,
+                      _chk(blank, "blank", torch.int32), ctypes.c_void_p(ev[0].cuda_event), ctypes.c_void_p(ev[1].cuda_event), _stream())
+            events.append(ev)
+        torch.cuda.synchronize()
+        own = [1e3 * a.elapsed_time(b) for a, b in events[1:]]
+        us, floor_us = float(np.median(own)), 2 * 3 * h * w / HBM_BYTES_PER_S * 1e6
+        row = {"h": h, "w": w, "model": "OPENCV", "kernel_us": round(us, 3), "kernel_us_min": round(min(own), 3), "floor_us": round(floor_us, 3),
+               "floor_what": "3 H W bytes read + 3 H W bytes written at 8 TB/s", "times_floor": round(us / floor_us, 2),
+               "blank_fraction": int(blank.item()) / (h * w)}
+        dec, enc = host_codec_ms(h, w)
+        row["host_codec_ms"] = {"jpeg_decode": dec, "jpeg_encode_q95": enc, "kernel_share": round(us * 1e-3 / (dec + enc + us * 1e-3), 5)}
+        got, got_blank = CI.undistort_image(src, cam, dist)
+        row["two_runs_identical"] = bool(torch.equal(got, out)) and got_blank == int(blank.item())
+        if cpu_baseline:
+            import undistort_oracle as UO
+            t0 = time.perf_counter()
+            want, want_blank = UO.undistort(img, cam, dist)
+            row["oracle_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+            row["bytes_equal_oracle"] = bool(np.array_equal(got.cpu().numpy(), want))
+            row["blank_equal_oracle"] = got_blank == want_blank
+        else:
+            row["oracle_ms"] = "not measured"
+        rows.append(row)
+    return {"sizes": "assumed", "timing": "the kernel's own start / stop timestamps, median of %d launches" % reps, "images": rows}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--phases", choices=("all", "import", "undistort"), default="all", help="import: pair scores, top views, depth ranks; "
+                    "undistort: the undistortion launch on two image sizes")
     ap.add_argument("--rocprof", default=None, help="directory: the three phases once in a child process under rocprofv3 --kernel-trace --stats")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--one-pass", action="store_true", help="(the profiled child) the three phases once, no timing")
@@ -49,6 +126,14 @@ def main():
     args = ap.parse_args()
     _lib.load()
     dev = "cuda:0"
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    if args.phases == "undistort":
+        text = json.dumps({"workload": "colmap_import", "undistort": undistort_phase(args.reps, not args.no_cpu_baseline, dev)})
+        print(text, flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     # every camera of the ring sees the whole box, so the frustum alone would give tracks of 300: observations are kept with the
     # probability that leaves about TRACK of them per point
     probe = synthetic.colmap_arrays(N_IMAGES, 20_000, hw=(1080, 1920), seed=0, arc_deg=300.0, keep=1.0)
@@ -92,7 +177,6 @@ def main():
     if args.no_cpu_baseline:
         line["cpu_baseline"] = "not measured"
     else:
-        sys.path.insert(0, os.path.join(REPO, "tests"))
         import colmap_oracle as O
         t0 = time.perf_counter()
         want, common = O.pair_scores(A["centres"], A["points"], A["offsets"], A["ids"])
@@ -109,6 +193,8 @@ def main():
         line["vs_oracle"] = {"max_score_error_over_bound": float((np.abs(got - want) / (1e-12 * (1 + common))).max()),
                              "top_lists_equal": bool(same_lists), "counts_equal": bool(np.array_equal(cnt.cpu().numpy(), wcnt)),
                              "depth_ranks_bit_identical": bool(np.array_equal(dr.cpu().numpy().view(np.int64), wdr.view(np.int64)))}
+    if args.phases == "all":
+        line["undistort"] = undistort_phase(args.reps, not args.no_cpu_baseline, dev)
     text = json.dumps(line)
     print(text, flush=True)
     if args.out:
