@@ -6,7 +6,8 @@ Two item sources: seeded synthetic DTU-shaped scenes (default), or real MVSNet-s
 ``rc_mvsnet_amd.mvs_dataset.MVSDataset`` (``--testpath`` + ``--testlist``), in which case the reference view's camera and image
 are written next to the depth maps as the reference does (eval_rcmvsnet_dtu.py:238-253) and ``--filter`` runs the fusion step
 (``rc_mvsnet_amd.fusion.filter_depth``, the reference's step 2) on this rank's scans.  With real data the shard unit is the scan,
-so that a rank owns every depth map its fusion needs.
+so that a rank owns every depth map its fusion needs.  ``--mesh`` (with ``--filter``) also meshes each scan into
+``<outdir>/<scan>_mesh.ply`` (``rc_mvsnet_amd.tsdf_mesh.mesh_scan``: TSDF fusion of the filtered depth maps, marching tetrahedra).
 
 ``--dataset tanks`` is the reference's Tanks-and-Temples workflow (``save_depth`` + ``__main__`` of eval_rcmvsnet_tanks.py:158-202,385-503)
 in one command: ``mvs_dataset.TanksDataset`` items through the model, ``depth_est/<view>.pfm``, ``confidence/<view>.pfm`` and the
@@ -23,6 +24,7 @@ The shard unit is the scene.
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m rc_mvsnet_amd.eval_driver --outdir out ...
 """
 import argparse
+import json
 import os
 import sys
 import time
@@ -119,6 +121,13 @@ def run_scans(model, args, device, rank, world):
             fusion.filter_depth(os.path.join(args.testpath, scan), folder, folder, os.path.join(args.outdir, scan + ".ply"),
                                 args.prob_thres, args.num_consistency, args.img_dist_thres, args.depth_thres,
                                 num_stage=nstage, device=str(device))
+            if args.mesh:
+                from . import tsdf_mesh
+                summary = tsdf_mesh.mesh_scan(os.path.join(args.testpath, scan), folder, folder, os.path.join(args.outdir, scan + "_mesh.ply"),
+                                              args.prob_thres, args.num_consistency, args.img_dist_thres, args.depth_thres, num_stage=nstage,
+                                              voxel=args.mesh_voxel, resolution=args.mesh_resolution, trunc_voxels=args.mesh_trunc_voxels,
+                                              device=str(device))
+                print(json.dumps(summary))
             if args.dtu_gt:
                 score_scan(args, scan, device)
     if times:
@@ -239,6 +248,11 @@ def main(argv=None):
     ap.add_argument("--max_w", type=int, default=None, help="default 1600 (dtu), 1920 (tanks)")
     ap.add_argument("--io_threads", type=int, default=4, help="threads decoding input images ahead / writing outputs behind the GPU")
     ap.add_argument("--filter", action="store_true", help="fuse each scan's depth maps into <outdir>/<scan>.ply afterwards")
+    ap.add_argument("--mesh", action="store_true", help="with --filter: also mesh each scan (TSDF fusion + marching tetrahedra, "
+                                                        "rc_mvsnet_amd.tsdf_mesh) into <outdir>/<scan>_mesh.ply")
+    ap.add_argument("--mesh-voxel", type=float, default=None, help="--mesh: voxel edge in world units (default: longest side / --mesh-resolution)")
+    ap.add_argument("--mesh-resolution", type=int, default=256, help="--mesh: voxels along the longest side of the cloud's bounding box")
+    ap.add_argument("--mesh-trunc-voxels", type=float, default=3.0, help="--mesh: truncation distance in voxels")
     ap.add_argument("--dtu-gt", default=None, help="DTU MVS_Data folder: after --filter, score each fused cloud (accuracy / completeness, "
                                                    "rc_mvsnet_amd.dtu_eval)")
     ap.add_argument("--prob_thres", type=float, default=0.8)
@@ -268,6 +282,8 @@ def main(argv=None):
         tanks_scenes(args)                                              # argument errors end here, before any rank starts or the network is built
     if args.dtu_gt and not args.filter:
         raise SystemExit("eval_driver: --dtu-gt scores the clouds of --filter; give both")
+    if args.mesh and (not args.filter or tanks or not args.testpath):
+        raise SystemExit("eval_driver: --mesh meshes the depth maps --filter fuses (real-layout DTU data: --testpath, --filter); give both")
     nproc = args.gpus * args.procs_per_gpu
     if nproc > 1 and not launched():
         raise SystemExit(launch_ranks("rc_mvsnet_amd.eval_driver", nproc, sys.argv[1:] if argv is None else argv, module=True))

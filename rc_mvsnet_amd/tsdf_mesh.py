@@ -1,0 +1,242 @@
+"""Depth maps -> triangle mesh on the HIP path: TSDF fusion into a dense voxel grid and marching tetrahedra
+(csrc/tsdf_mesh.hip; the contract is csrc/tsdf_mesh.h, the arithmetic csrc/tsdf_mesh_math.h, restated by tests/tsdf_oracle.py).
+
+``TsdfVolume`` holds the planar fp32 state on the device; ``integrate`` adds views sixteen to a launch (a voxel's state is read
+and written once per launch, and the result does not depend on the chunking), ``extract`` runs count / scan / emit and returns
+vertices, faces and vertex colours as device tensors.  ``mesh_scan`` is the mesh counterpart of ``fusion.filter_depth``: the same
+``fusion.fuse_view`` per reference view, its filtered ``depth_avg`` integrated instead of back-projected, one PLY written.
+
+    python -m rc_mvsnet_amd.tsdf_mesh --pair-folder data/scan9 --scan-folder out/scan9 --out-folder out/scan9 --mesh out/scan9_mesh.ply
+
+Limits: the grid is dense and axis-aligned, at most 2^28 voxels (a large outdoor scene gets coarse voxels; a sparse or hashed
+volume is out of scope); no hole filling, smoothing or decimation; marching tetrahedra emits roughly twice the triangles of
+marching cubes; vertices at the rim of the observed region can end up unreferenced.  No CPU fallback."""
+import argparse
+import ctypes
+import json
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, fusion, scan_io
+from .data_io import read_pfm
+
+MAX_VOXELS, MAX_VIEWS, SCAN_TILE = (_lib.CONSTANTS[k] for k in ("RCMVS_TSDF_MAX_VOXELS", "RCMVS_TSDF_MAX_VIEWS", "RCMVS_TSDF_SCAN_TILE"))
+_NULL = ctypes.c_void_p(0)
+
+
+def _ptr(t, name, dtype):
+    return _NULL if t is None else fusion._chk(t, name, dtype)
+
+
+class TsdfVolume:
+    """A gx x gy x gz grid of cubic voxels of edge ``voxel`` with its lower corner at ``origin``; voxel (i, j, k) is number
+    i + gx * (j + gy * k) and has its centre at origin + (idx + 0.5) * voxel."""
+
+    def __init__(self, origin, voxel, dims, device, colour=True):
+        self.grid = [float(origin[0]), float(origin[1]), float(origin[2]), float(voxel)]
+        self.dims = [int(d) for d in dims]
+        if len(self.dims) != 3 or min(self.dims) < 1 or self.dims[0] * self.dims[1] * self.dims[2] > MAX_VOXELS:
+            raise _lib.RcmvsError(f"TsdfVolume: dims {self.dims} (three sides >= 1, at most 2^28 voxels)")
+        if not all(math.isfinite(v) for v in self.grid) or not self.grid[3] > 0:
+            raise _lib.RcmvsError(f"TsdfVolume: origin {self.grid[:3]}, voxel {self.grid[3]} (finite, voxel positive)")
+        self.voxels = self.dims[0] * self.dims[1] * self.dims[2]
+        self.device = torch.device(device)
+        self.dsum = torch.zeros(self.voxels, device=self.device, dtype=torch.float32)
+        self.wsum = torch.zeros(self.voxels, device=self.device, dtype=torch.float32)
+        self.csum = [torch.zeros(self.voxels, device=self.device, dtype=torch.float32) for _ in range(3)] if colour else None
+
+    def _host(self):
+        return (ctypes.c_double * 4)(*self.grid), (ctypes.c_int * 3)(*self.dims)
+
+    def _colour_ptrs(self):
+        return [_ptr(None if self.csum is None else self.csum[c], "csum", torch.float32) for c in range(3)]
+
+    def integrate(self, depth, cams, rgb=None, trunc=None):
+        """depth (n,H,W) fp32 and rgb (n,H,W,3) uint8 (or None) on the device, cams (n,16) {R row-major 9, t 3, fx, fy, cx, cy}
+        world -> camera on the host; any n, sixteen views to a launch."""
+        if trunc is None:
+            raise _lib.RcmvsError("TsdfVolume.integrate: trunc (the truncation distance, in world units) is required")
+        if depth.dim() != 3:
+            raise _lib.RcmvsError(f"TsdfVolume.integrate: expected (n,H,W) depth maps, got {tuple(depth.shape)}")
+        n, H, W = (int(s) for s in depth.shape)
+        cams = np.ascontiguousarray(np.asarray(cams, dtype=np.float64).reshape(-1, 16))
+        if len(cams) != n or (rgb is not None and tuple(rgb.shape) != (n, H, W, 3)):
+            raise _lib.RcmvsError(f"TsdfVolume.integrate: {n} depth maps of {H} x {W}, {len(cams)} cameras, rgb {None if rgb is None else tuple(rgb.shape)}")
+        grid, dims = self._host()
+        for lo in range(0, n, MAX_VIEWS):
+            hi = min(lo + MAX_VIEWS, n)
+            _lib.call("rcmvs_tsdf_integrate", fusion._chk(depth[lo:hi], "depth"), _ptr(None if rgb is None else rgb[lo:hi], "rgb", torch.uint8),
+                      hi - lo, H, W, cams[lo:hi].ctypes.data_as(ctypes.c_void_p), float(trunc), grid, dims, fusion._chk(self.dsum, "dsum"),
+                      fusion._chk(self.wsum, "wsum"), *self._colour_ptrs(), fusion._stream())
+        return self
+
+    def count(self, min_weight=1):
+        """-> (edge_mask, tri_count (uint8 per voxel), vert_start, tri_start (voxels + 1 int32), (vertices, faces) as ints)"""
+        dev, n = self.device, self.voxels
+        edge_mask = torch.empty(n, device=dev, dtype=torch.uint8)
+        tri_count = torch.empty(n, device=dev, dtype=torch.uint8)
+        work = torch.empty(256 + 2 * ((n + SCAN_TILE - 1) // SCAN_TILE), device=dev, dtype=torch.int32)
+        vert_start = torch.empty(n + 1, device=dev, dtype=torch.int32)
+        tri_start = torch.empty(n + 1, device=dev, dtype=torch.int32)
+        totals = torch.empty(2, device=dev, dtype=torch.int64)
+        _lib.call("rcmvs_tsdf_mesh_count", fusion._chk(self.dsum, "dsum"), fusion._chk(self.wsum, "wsum"), self._host()[1], int(min_weight),
+                  fusion._chk(edge_mask, "edge_mask", torch.uint8), fusion._chk(tri_count, "tri_count", torch.uint8),
+                  fusion._chk(work, "scan_work", torch.int32), fusion._chk(vert_start, "vert_start", torch.int32),
+                  fusion._chk(tri_start, "tri_start", torch.int32), fusion._chk(totals, "totals", torch.int64), fusion._stream())
+        nv, nf = (int(t) for t in totals.cpu())                      # the one host synchronisation of an extraction
+        return edge_mask, tri_count, vert_start, tri_start, (nv, nf)
+
+    def extract(self, min_weight=1):
+        """-> (verts (nv,3) fp32, faces (nf,3) int32, rgb (nv,3) uint8 or None without colour planes), device tensors"""
+        edge_mask, tri_count, vert_start, tri_start, (nv, nf) = self.count(min_weight)
+        if nv >= 1 << 31 or nf >= 1 << 31:
+            raise _lib.RcmvsError(f"TsdfVolume.extract: {nv} vertices, {nf} faces (below 2^31 each): use larger voxels")
+        dev = self.device
+        verts = torch.empty((nv, 3), device=dev, dtype=torch.float32)
+        faces = torch.empty((nf, 3), device=dev, dtype=torch.int32)
+        rgb = torch.empty((nv, 3), device=dev, dtype=torch.uint8) if self.csum is not None else None
+        grid, dims = self._host()
+        _lib.call("rcmvs_tsdf_mesh_emit", fusion._chk(self.dsum, "dsum"), fusion._chk(self.wsum, "wsum"), *self._colour_ptrs(), grid, dims,
+                  int(min_weight), fusion._chk(edge_mask, "edge_mask", torch.uint8), fusion._chk(tri_count, "tri_count", torch.uint8),
+                  fusion._chk(vert_start, "vert_start", torch.int32), fusion._chk(tri_start, "tri_start", torch.int32), nv, nf,
+                  _ptr(verts if nv else None, "verts", torch.float32), _ptr(rgb if nv else None, "vert_rgb", torch.uint8),
+                  _ptr(faces if nf else None, "faces", torch.int32), fusion._stream())
+        return verts, faces, rgb
+
+
+def mesh_ply_bytes(verts, faces, rgb=None):
+    """Binary little-endian PLY of a triangle mesh: vertex properties x y z (float) red green blue (uchar), then ``element face``
+    with ``property list uchar int vertex_indices``.  rgb None: white.  dtu_io.read_ply_mesh reads it back exactly."""
+    verts, faces = (t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in (verts, faces))
+    rgb = None if rgb is None else (rgb.cpu().numpy() if torch.is_tensor(rgb) else np.asarray(rgb))
+    nv, nf = len(verts), len(faces)
+    head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %d\nproperty list uchar int vertex_indices\n"
+            "end_header\n" % (nv, nf)).encode("ascii")
+    vrec = np.empty(nv, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    for i, k in enumerate(("x", "y", "z")):
+        vrec[k] = verts[:, i] if nv else 0
+    for i, k in enumerate(("red", "green", "blue")):
+        vrec[k] = 255 if rgb is None else rgb[:, i]
+    frec = np.empty(nf, dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    frec["n"] = 3
+    frec["v"] = faces.reshape(nf, 3)
+    return head + vrec.tobytes() + frec.tobytes()
+
+
+def camera_row(K, E):
+    """(3,3) intrinsics and (4,4) world -> camera extrinsics -> the 16 doubles of rcmvs_tsdf_integrate"""
+    K, E = np.asarray(K, np.float64), np.asarray(E, np.float64)
+    return np.concatenate([E[:3, :3].ravel(), E[:3, 3], [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]])
+
+
+def filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage=3,
+                   device="cuda:0"):
+    """fusion.fuse_view per reference view of pair.txt, as filter_depth runs it -> dict: depth (V,H,W) fp32 = depth_avg where the
+    final mask holds and 0 elsewhere, rgb (V,H,W,3) uint8, both on the device; cams (V,16) float64; lo, hi: the bounding box of
+    the surviving points (float64, None when no point survives)."""
+    dev = torch.device(device)
+    pairs = scan_io.read_pair_file(os.path.join(pair_folder, "pair.txt"))
+    views = sorted({v for ref, srcs in pairs for v in [ref] + list(srcs)})
+    slot = {v: i for i, v in enumerate(views)}
+    cams = {v: scan_io.read_camera_parameters(os.path.join(scan_folder, "cams/{:0>8}_cam.txt".format(v))) for v in views}
+    depth_all = torch.from_numpy(np.stack([read_pfm(os.path.join(out_folder, "depth_est/{:0>8}.pfm".format(v)))[0] for v in views])).to(dev)
+    depths, colours, rows, lo, hi = [], [], [], None, None
+    for ref, srcs in pairs:
+        if len(srcs) > fusion.MAX_SRC:
+            raise _lib.RcmvsError(f"mesh_scan: view {ref} lists {len(srcs)} source views (at most {fusion.MAX_SRC})")
+        conf = torch.from_numpy(read_pfm(os.path.join(out_folder, "confidence/{:0>8}.pfm".format(ref)))[0]).to(dev)
+        img = scan_io.read_img(os.path.join(scan_folder, "images/{:0>8}.jpg".format(ref)))
+        img = torch.from_numpy(fusion.stage_colour(img, num_stage, conf.shape)).to(dev)
+        mats = torch.from_numpy(fusion.fusion_matrices(cams[ref][0], cams[ref][1], [cams[s][0] for s in srcs], [cams[s][1] for s in srcs])).to(dev)
+        r = fusion.fuse_view(depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, prob_threshold, num_consistent, img_dist_thresh,
+                             depth_thresh)
+        keep = r["masks"][2] != 0
+        depths.append(torch.where(keep, r["depth_avg"], torch.zeros_like(r["depth_avg"])))
+        colours.append(r["rgb"])
+        rows.append(camera_row(*cams[ref]))
+        if bool(keep.any()):
+            pts = r["xyz"][keep].double()
+            pts = pts[torch.isfinite(pts).all(1)]
+            if len(pts):
+                a, b = pts.min(0).values.cpu().numpy(), pts.max(0).values.cpu().numpy()
+                lo, hi = (a, b) if lo is None else (np.minimum(lo, a), np.maximum(hi, b))
+    return {"depth": torch.stack(depths).contiguous(), "rgb": torch.stack(colours).contiguous(), "cams": np.stack(rows), "lo": lo, "hi": hi}
+
+
+def plan_grid(lo, hi, voxel=None, resolution=256, trunc_voxels=3.0, pad=True):
+    """The grid of a box lo .. hi (float64): voxel defaults to the longest side / resolution, trunc = trunc_voxels * voxel, the
+    box is padded by trunc on every side (pad=False: explicit bounds are taken as they are) -> (origin, voxel, dims, trunc)."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all()):
+        raise _lib.RcmvsError(f"mesh_scan: bad bounds {lo} .. {hi}")
+    if voxel is None:
+        voxel = float((hi - lo).max()) / int(resolution)
+    voxel = float(voxel)
+    if not (math.isfinite(voxel) and voxel > 0 and math.isfinite(trunc_voxels) and trunc_voxels > 0):
+        raise _lib.RcmvsError(f"mesh_scan: voxel {voxel}, trunc_voxels {trunc_voxels} (finite, positive; a box without extent needs --voxel)")
+    trunc = float(trunc_voxels) * voxel
+    if pad:
+        lo, hi = lo - trunc, hi + trunc
+    dims = [max(1, int(math.ceil(float(s) / voxel))) for s in (hi - lo)]
+    if dims[0] * dims[1] * dims[2] > MAX_VOXELS:
+        raise _lib.RcmvsError(f"mesh_scan: {dims[0]} x {dims[1]} x {dims[2]} voxels of {voxel} (at most 2^28): use larger voxels or tighter bounds")
+    return [float(v) for v in lo], voxel, dims, trunc
+
+
+def mesh_scan(pair_folder, scan_folder, out_folder, meshfilename, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage=3,
+              voxel=None, resolution=256, trunc_voxels=3.0, min_weight=1, bounds=None, device="cuda:0"):
+    """Mesh one scan laid out as fusion.filter_depth reads it into ``meshfilename``.  bounds: (xmin, ymin, zmin, xmax, ymax, zmax),
+    default the bounding box of the points that survive the filter, padded by the truncation distance.  Returns the summary dict."""
+    views = filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage, device)
+    if bounds is not None:
+        b = [float(v) for v in bounds]
+        if len(b) != 6:
+            raise _lib.RcmvsError("mesh_scan: bounds are xmin ymin zmin xmax ymax zmax")
+        origin, voxel, dims, trunc = plan_grid(b[:3], b[3:], voxel, resolution, trunc_voxels, pad=False)
+    else:
+        if views["lo"] is None:
+            raise _lib.RcmvsError("mesh_scan: no point survives the filter, so there is no bounding box; give bounds")
+        origin, voxel, dims, trunc = plan_grid(views["lo"], views["hi"], voxel, resolution, trunc_voxels)
+    vol = TsdfVolume(origin, voxel, dims, device)
+    vol.integrate(views["depth"], views["cams"], views["rgb"], trunc=trunc)
+    verts, faces, rgb = vol.extract(min_weight)
+    os.makedirs(os.path.dirname(os.path.abspath(meshfilename)), exist_ok=True)
+    with open(meshfilename, "wb") as f:
+        f.write(mesh_ply_bytes(verts, faces, rgb))
+    referenced = int(torch.unique(faces).numel())
+    return {"mesh": meshfilename, "origin": origin, "dims": dims, "voxel": voxel, "trunc": trunc, "min_weight": int(min_weight),
+            "views": int(views["depth"].shape[0]), "vertices": int(verts.shape[0]), "faces": int(faces.shape[0]),
+            "unreferenced_vertices": int(verts.shape[0]) - referenced, "observed_voxels": int((vol.wsum >= float(min_weight)).sum())}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="TSDF fusion + marching tetrahedra of one scan's depth maps into a PLY mesh")
+    ap.add_argument("--pair-folder", required=True, help="folder of pair.txt")
+    ap.add_argument("--scan-folder", required=True, help="folder of cams/ and images/")
+    ap.add_argument("--out-folder", required=True, help="folder of depth_est/ and confidence/")
+    ap.add_argument("--mesh", required=True, help="the PLY to write")
+    ap.add_argument("--prob_thres", type=float, default=0.8)
+    ap.add_argument("--num_consistency", type=int, default=3)
+    ap.add_argument("--img_dist_thres", type=float, default=0.5)
+    ap.add_argument("--depth_thres", type=float, default=0.01)
+    ap.add_argument("--num-stage", type=int, default=3)
+    ap.add_argument("--voxel", type=float, default=None, help="voxel edge in world units (default: longest side / --resolution)")
+    ap.add_argument("--resolution", type=int, default=256)
+    ap.add_argument("--trunc-voxels", type=float, default=3.0, help="truncation distance in voxels")
+    ap.add_argument("--min-weight", type=int, default=1, help="views a voxel must have been seen by")
+    ap.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("XMIN", "YMIN", "ZMIN", "XMAX", "YMAX", "ZMAX"))
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    summary = mesh_scan(a.pair_folder, a.scan_folder, a.out_folder, a.mesh, a.prob_thres, a.num_consistency, a.img_dist_thres, a.depth_thres,
+                        num_stage=a.num_stage, voxel=a.voxel, resolution=a.resolution, trunc_voxels=a.trunc_voxels, min_weight=a.min_weight,
+                        bounds=a.bounds, device=a.device)
+    print(json.dumps(summary))
+    return summary
+
+
+if __name__ == "__main__":
+    main()
