@@ -18,14 +18,12 @@
 #include "common.h"
 #include "tsdf_mesh.h"
 #include "tsdf_mesh_math.h"
+#include "tsdf_mesh_cells.h"
 
 #pragma clang fp contract(off)
 
 namespace rcmvs {
 
-constexpr int TM_BLOCK = 256;
-constexpr int TM_TILE = RCMVS_TSDF_SCAN_TILE;
-constexpr int TM_PER = TM_TILE / TM_BLOCK;                        // 8 voxels (or tile sums) per thread
 constexpr int TM_TOP = 64;                                        // at most ceil(2^28 / 2048 / 2048) sums at the top level
 
 // ---- integrate --------------------------------------------------------------------------------------------------------------
@@ -41,38 +39,16 @@ __global__ __launch_bounds__(TM_BLOCK) void tsdf_integrate_kernel(const float* _
     const bool colour = rgb != nullptr && cr != nullptr;
     float d = dsum[v], w = wsum[v], r = 0.0f, gr = 0.0f, b = 0.0f;
     if (colour) { r = cr[v]; gr = cg[v]; b = cb[v]; }
-    const size_t plane = (size_t)H * (size_t)W;
-    for (int s = 0; s < n; ++s) {
-        double val;
-        int pix;
-        if (!tsdf::observe(cams.c[s], px, py, pz, depth + (size_t)s * plane, H, W, trunc, &val, &pix)) continue;
-        d += (float)val;
-        w += 1.0f;
-        if (colour) {
-            const unsigned char* c = rgb + ((size_t)s * plane + (size_t)pix) * 3;
-            r += (float)c[0];
-            gr += (float)c[1];
-            b += (float)c[2];
-        }
-    }
-    dsum[v] = d;
-    wsum[v] = w;
-    if (colour) { cr[v] = r; cg[v] = gr; cb[v] = b; }
+    const TmState s = tm_integrate_voxel(depth, rgb, n, H, W, cams, trunc, px, py, pz, colour, TmState{d, w, r, gr, b});
+    dsum[v] = s.d;
+    wsum[v] = s.w;
+    if (colour) { cr[v] = s.r; cg[v] = s.g; cb[v] = s.b; }
 }
 
 // ---- the field as the extraction sees it ------------------------------------------------------------------------------------
 struct TmDims {
     int gx, gy, gz;
 };
-
-// bit 0: observed, bit 1: inside.  With w >= min_weight >= 1 the value (double)dsum / (double)w is < 0 exactly when dsum < 0 and w
-// is finite (the quotient of an fp32 by an fp32 cannot underflow in fp64; dsum / inf is -0, which is not < 0), so the flags need
-// no division; the emit kernel divides where it needs the value itself.
-__device__ inline int tm_flags(const float* __restrict__ dsum, const float* __restrict__ wsum, int v, float min_weight) {
-    const float w = wsum[v];
-    if (!(w >= min_weight)) return 0;
-    return (dsum[v] < 0.0f && w <= 3.402823466e+38f) ? 3 : 1;
-}
 
 // the flags of the eight voxels at codes 0..7 from (i, j, k); a neighbour beyond the grid is unobserved
 __device__ inline void tm_corner_flags(const float* __restrict__ dsum, const float* __restrict__ wsum, TmDims g, int i, int j, int k, float min_weight,
@@ -84,55 +60,7 @@ __device__ inline void tm_corner_flags(const float* __restrict__ dsum, const flo
     }
 }
 
-__device__ inline unsigned tm_edge_mask(const int* f) {
-    unsigned m = 0;
-    if (f[0] & 1) {
-#pragma unroll
-        for (int c = 1; c < 8; ++c)
-            if ((f[c] & 1) && ((f[c] ^ f[0]) & 2)) m |= 1u << (c - 1);
-    }
-    return m;
-}
-
-// the case of tetrahedron t, or 0 (no triangles) when one of its corners is not observed
-__device__ inline int tm_tet_case(const int* f, int t) {
-    int m = 0, obs = 1;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int fl = f[tsdf::tet_corner(t, c)];
-        obs &= fl;
-        m |= ((fl >> 1) & 1) << c;
-    }
-    return (obs & 1) ? m : 0;
-}
-
 // ---- count ------------------------------------------------------------------------------------------------------------------
-__device__ inline unsigned tm_block_sum(unsigned v, unsigned* sh) {     // sum of v over the block, in every thread; sh: TM_BLOCK
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = TM_BLOCK / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    const unsigned r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ inline unsigned tm_block_exclusive(unsigned v, unsigned* sh) {   // exclusive prefix of v over the block; sh: TM_BLOCK
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < TM_BLOCK; o <<= 1) {
-        const unsigned t = (int)threadIdx.x >= o ? sh[threadIdx.x - o] : 0u;
-        __syncthreads();
-        sh[threadIdx.x] += t;
-        __syncthreads();
-    }
-    const unsigned r = sh[threadIdx.x] - v;
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(TM_BLOCK) void tsdf_count_kernel(const float* __restrict__ dsum, const float* __restrict__ wsum, TmDims g, int voxels,
                                                               float min_weight, unsigned char* __restrict__ edge_mask,
                                                               unsigned char* __restrict__ tri_count, unsigned* __restrict__ tile_v,
@@ -157,49 +85,6 @@ __global__ __launch_bounds__(TM_BLOCK) void tsdf_count_kernel(const float* __res
     }
     const unsigned sv = tm_block_sum(nv, sh), st = tm_block_sum(nt, sh);
     if (threadIdx.x == 0) { tile_v[blockIdx.x] = sv; tile_t[blockIdx.x] = st; }
-}
-
-// sums of TM_TILE tile sums, in 64 bits
-__global__ __launch_bounds__(TM_BLOCK) void tsdf_scan_up_kernel(const unsigned* __restrict__ tile_v, const unsigned* __restrict__ tile_t, int nb1,
-                                                                unsigned long long* __restrict__ top) {
-    __shared__ unsigned long long sh[2][TM_BLOCK];
-    const long long base = (long long)blockIdx.x * TM_TILE + (long long)threadIdx.x * TM_PER;
-    unsigned long long a = 0, b = 0;
-    for (int q = 0; q < TM_PER; ++q)
-        if (base + q < nb1) { a += tile_v[base + q]; b += tile_t[base + q]; }
-    sh[0][threadIdx.x] = a;
-    sh[1][threadIdx.x] = b;
-    __syncthreads();
-    for (int o = TM_BLOCK / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { sh[0][threadIdx.x] += sh[0][threadIdx.x + o]; sh[1][threadIdx.x] += sh[1][threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { top[blockIdx.x] = sh[0][0]; top[TM_TOP + blockIdx.x] = sh[1][0]; }
-}
-
-// the top level in place: top[0..nb2) and top[TM_TOP..TM_TOP+nb2) -> exclusive prefixes; totals = the two sums
-__global__ void tsdf_scan_top_kernel(unsigned long long* __restrict__ top, int nb2, unsigned long long* __restrict__ totals) {
-    if (threadIdx.x > 1 || blockIdx.x != 0) return;
-    unsigned long long* t = top + (size_t)threadIdx.x * TM_TOP;
-    unsigned long long run = 0;
-    for (int b = 0; b < nb2; ++b) { const unsigned long long c = t[b]; t[b] = run; run += c; }
-    totals[threadIdx.x] = run;
-}
-
-// tile sums -> their exclusive prefixes, in place (32 bit, wrapping)
-__global__ __launch_bounds__(TM_BLOCK) void tsdf_scan_mid_kernel(unsigned* __restrict__ tile_v, unsigned* __restrict__ tile_t, int nb1,
-                                                                 const unsigned long long* __restrict__ top) {
-    __shared__ unsigned sh[TM_BLOCK];
-    const long long base = (long long)blockIdx.x * TM_TILE + (long long)threadIdx.x * TM_PER;
-    for (int which = 0; which < 2; ++which) {
-        unsigned* tile = which ? tile_t : tile_v;
-        unsigned c[TM_PER], s = 0;
-#pragma unroll
-        for (int q = 0; q < TM_PER; ++q) { c[q] = base + q < nb1 ? tile[base + q] : 0u; s += c[q]; }
-        unsigned run = tm_block_exclusive(s, sh) + (unsigned)top[which * TM_TOP + blockIdx.x];
-#pragma unroll
-        for (int q = 0; q < TM_PER; ++q) { if (base + q < nb1) tile[base + q] = run; run += c[q]; }
-    }
 }
 
 __global__ __launch_bounds__(TM_BLOCK) void tsdf_scan_down_kernel(const unsigned char* __restrict__ edge_mask, const unsigned char* __restrict__ tri_count,
@@ -369,9 +254,9 @@ extern "C" int rcmvs_tsdf_mesh_count_timed(const float* dsum, const float* wsum,
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
     RCMVS_LAUNCH_TIMED(tsdf_count_kernel, dim3(nb1), dim3(TM_BLOCK), 0, st, e0, none, dsum, wsum, g, (int)voxels, (float)min_weight, edge_mask, tri_count,
                        tile_v, tile_t);
-    hipLaunchKernelGGL(tsdf_scan_up_kernel, dim3(nb2), dim3(TM_BLOCK), 0, st, tile_v, tile_t, nb1, top);
-    hipLaunchKernelGGL(tsdf_scan_top_kernel, dim3(1), dim3(64), 0, st, top, nb2, totals);
-    hipLaunchKernelGGL(tsdf_scan_mid_kernel, dim3(nb2), dim3(TM_BLOCK), 0, st, tile_v, tile_t, nb1, top);
+    hipLaunchKernelGGL(tsdf_scan_up_kernel<TM_TOP>, dim3(nb2), dim3(TM_BLOCK), 0, st, tile_v, tile_t, nb1, top);
+    hipLaunchKernelGGL(tsdf_scan_top_kernel<TM_TOP>, dim3(1), dim3(64), 0, st, top, nb2, totals);
+    hipLaunchKernelGGL(tsdf_scan_mid_kernel<TM_TOP>, dim3(nb2), dim3(TM_BLOCK), 0, st, tile_v, tile_t, nb1, top);
     RCMVS_LAUNCH_TIMED(tsdf_scan_down_kernel, dim3(nb1), dim3(TM_BLOCK), 0, st, none, e1, edge_mask, tri_count, (int)voxels, tile_v, tile_t, totals,
                        vert_start, tri_start);
     return launch_status("tsdf_mesh_count");

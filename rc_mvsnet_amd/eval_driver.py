@@ -126,7 +126,7 @@ def run_scans(model, args, device, rank, world):
                 summary = tsdf_mesh.mesh_scan(os.path.join(args.testpath, scan), folder, folder, os.path.join(args.outdir, scan + "_mesh.ply"),
                                               args.prob_thres, args.num_consistency, args.img_dist_thres, args.depth_thres, num_stage=nstage,
                                               voxel=args.mesh_voxel, resolution=args.mesh_resolution, trunc_voxels=args.mesh_trunc_voxels,
-                                              device=str(device))
+                                              device=str(device), sparse=args.mesh_sparse)
                 print(json.dumps(summary))
             if args.dtu_gt:
                 score_scan(args, scan, device)
@@ -208,6 +208,14 @@ def run_tanks(model, args, device, rank, world):
         fusion.filter_depth_tanks(os.path.join(args.testpath, args.split, scene), os.path.join(args.outdir, scene), ply, f["geo_pixel_thres"],
                                   f["geo_depth_thres"], f["photo_thres"], img_wh, f["image_size"], f["geo_mask_thres"], args.num_view, scene,
                                   device=str(device), depth_maps=depth_maps, conf_maps=conf_maps)
+        if args.mesh:
+            from . import tsdf_mesh
+            summary = tsdf_mesh.mesh_scan_tanks(os.path.join(args.testpath, args.split, scene), os.path.join(args.outdir, scene),
+                                                os.path.join(args.plydir, scene + "_mesh.ply"), f["geo_pixel_thres"], f["geo_depth_thres"],
+                                                f["photo_thres"], img_wh, f["image_size"], f["geo_mask_thres"], args.num_view, scene,
+                                                device=str(device), depth_maps=depth_maps, conf_maps=conf_maps, voxel=args.mesh_voxel,
+                                                resolution=args.mesh_resolution or 1024, trunc_voxels=args.mesh_trunc_voxels)
+            print(json.dumps(summary))
         del depth_maps, conf_maps
     if times:
         warm = times[1:] or times
@@ -251,7 +259,9 @@ def main(argv=None):
     ap.add_argument("--mesh", action="store_true", help="with --filter: also mesh each scan (TSDF fusion + marching tetrahedra, "
                                                         "rc_mvsnet_amd.tsdf_mesh) into <outdir>/<scan>_mesh.ply")
     ap.add_argument("--mesh-voxel", type=float, default=None, help="--mesh: voxel edge in world units (default: longest side / --mesh-resolution)")
-    ap.add_argument("--mesh-resolution", type=int, default=256, help="--mesh: voxels along the longest side of the cloud's bounding box")
+    ap.add_argument("--mesh-resolution", type=int, default=None, help="--mesh: voxels along the longest side of the cloud's bounding box "
+                                                                      "(default 256; 1024 with --mesh-sparse and for tanks)")
+    ap.add_argument("--mesh-sparse", action="store_true", help="--mesh: a block-sparse volume (tsdf_mesh.SparseTsdfVolume); tanks always uses it")
     ap.add_argument("--mesh-trunc-voxels", type=float, default=3.0, help="--mesh: truncation distance in voxels")
     ap.add_argument("--dtu-gt", default=None, help="DTU MVS_Data folder: after --filter, score each fused cloud (accuracy / completeness, "
                                                    "rc_mvsnet_amd.dtu_eval)")
@@ -282,7 +292,7 @@ def main(argv=None):
         tanks_scenes(args)                                              # argument errors end here, before any rank starts or the network is built
     if args.dtu_gt and not args.filter:
         raise SystemExit("eval_driver: --dtu-gt scores the clouds of --filter; give both")
-    if args.mesh and (not args.filter or tanks or not args.testpath):
+    if args.mesh and not tanks and (not args.filter or not args.testpath):
         raise SystemExit("eval_driver: --mesh meshes the depth maps --filter fuses (real-layout DTU data: --testpath, --filter); give both")
     nproc = args.gpus * args.procs_per_gpu
     if nproc > 1 and not launched():

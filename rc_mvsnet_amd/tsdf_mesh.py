@@ -8,9 +8,16 @@ vertices, faces and vertex colours as device tensors.  ``mesh_scan`` is the mesh
 
     python -m rc_mvsnet_amd.tsdf_mesh --pair-folder data/scan9 --scan-folder out/scan9 --out-folder out/scan9 --mesh out/scan9_mesh.ply
 
-Limits: the grid is dense and axis-aligned, at most 2^28 voxels (a large outdoor scene gets coarse voxels; a sparse or hashed
-volume is out of scope); no hole filling, smoothing or decimation; marching tetrahedra emits roughly twice the triangles of
-marching cubes; vertices at the rim of the observed region can end up unreferenced.  No CPU fallback."""
+``SparseTsdfVolume`` (csrc/tsdf_sparse.hip, contract csrc/tsdf_sparse.h) is the volume of a large scene: 8 x 8 x 8-voxel blocks
+allocated only where the truncation slab of a depth pixel passes (mark, build), then the same integrate / extract per allocated
+voxel.  With no skipped pixel its mesh is the dense mesh of the same grid in another order.  ``mesh_scan(sparse=True)``, ``--sparse``
+and ``mesh_scan_tanks`` use it.
+
+Limits: both volumes are axis-aligned.  The dense grid has at most 2^28 voxels; the sparse one at most 2^27 blocks (4096^3 voxels) of
+which at most 2^19 are active, its block set does not grow after build(), and a pixel whose slab spans more than 4 blocks on an
+axis is skipped and counted (with any skipped pixel the equality with the dense mesh is no longer guaranteed).  No hole filling,
+smoothing or decimation; marching tetrahedra emits roughly twice the triangles of marching cubes; vertices at the rim of the
+observed region can end up unreferenced.  No CPU fallback."""
 import argparse
 import ctypes
 import json
@@ -24,6 +31,8 @@ from . import _lib, fusion, scan_io
 from .data_io import read_pfm
 
 MAX_VOXELS, MAX_VIEWS, SCAN_TILE = (_lib.CONSTANTS[k] for k in ("RCMVS_TSDF_MAX_VOXELS", "RCMVS_TSDF_MAX_VIEWS", "RCMVS_TSDF_SCAN_TILE"))
+SP_BLOCK, SP_MAX_BLOCKS, SP_MAX_ACTIVE, SP_SCAN_TILE = (_lib.CONSTANTS["RCMVS_TSDF_SP_" + k] for k in ("BLOCK", "MAX_BLOCKS", "MAX_ACTIVE", "SCAN_TILE"))
+SP_VOXELS = SP_BLOCK ** 3
 _NULL = ctypes.c_void_p(0)
 
 
@@ -107,6 +116,135 @@ class TsdfVolume:
         return verts, faces, rgb
 
 
+class SparseTsdfVolume:
+    """A virtual grid of bx x by x bz blocks of 8 x 8 x 8 voxels of which only the marked blocks are allocated (csrc/tsdf_sparse.h).
+    The order is mark (any number of times; ``flags`` may also be written directly), build, integrate, count / extract; the block set
+    does not grow after build.  A voxel's planes equal TsdfVolume's planes of the same voxel in a grid of 8 * bdims voxels."""
+
+    def __init__(self, origin, voxel, bdims, device, colour=True):
+        self.grid = [float(origin[0]), float(origin[1]), float(origin[2]), float(voxel)]
+        self.bdims = [int(d) for d in bdims]
+        if len(self.bdims) != 3 or min(self.bdims) < 1 or self.bdims[0] * self.bdims[1] * self.bdims[2] > SP_MAX_BLOCKS:
+            raise _lib.RcmvsError(f"SparseTsdfVolume: bdims {self.bdims} (three sides >= 1, at most 2^27 blocks)")
+        if not all(math.isfinite(v) for v in self.grid) or not self.grid[3] > 0:
+            raise _lib.RcmvsError(f"SparseTsdfVolume: origin {self.grid[:3]}, voxel {self.grid[3]} (finite, voxel positive)")
+        self.blocks = self.bdims[0] * self.bdims[1] * self.bdims[2]
+        self.dims = [SP_BLOCK * b for b in self.bdims]
+        self.device = torch.device(device)
+        self.colour = bool(colour)
+        self.flags = torch.zeros(self.blocks, device=self.device, dtype=torch.uint8)
+        self._skipped = torch.zeros(1, device=self.device, dtype=torch.int64)
+        self.n_active = None                                        # set by build()
+
+    def _host(self):
+        return (ctypes.c_double * 4)(*self.grid), (ctypes.c_int * 3)(*self.bdims)
+
+    def _need(self, built, what):
+        if built != (self.n_active is not None):
+            raise _lib.RcmvsError(f"SparseTsdfVolume.{what}: " + ("call build() first" if built else "the block set is fixed by build()"))
+
+    def _colour_ptrs(self):
+        return [_ptr(None if self.csum is None else self.csum[c], "csum", torch.float32) for c in range(3)]
+
+    def _table(self):
+        return (fusion._chk(self.mask_words, "mask_words", torch.int32), fusion._chk(self.word_rank, "word_rank", torch.int32),
+                fusion._chk(self.active, "active", torch.int32), self.n_active)
+
+    @staticmethod
+    def _views(depth, cams, rgb, what):
+        if depth.dim() != 3:
+            raise _lib.RcmvsError(f"SparseTsdfVolume.{what}: expected (n,H,W) depth maps, got {tuple(depth.shape)}")
+        n, H, W = (int(s) for s in depth.shape)
+        cams = np.ascontiguousarray(np.asarray(cams, dtype=np.float64).reshape(-1, 16))
+        if len(cams) != n or (rgb is not None and tuple(rgb.shape) != (n, H, W, 3)):
+            raise _lib.RcmvsError(f"SparseTsdfVolume.{what}: {n} depth maps of {H} x {W}, {len(cams)} cameras, rgb {None if rgb is None else tuple(rgb.shape)}")
+        return n, H, W, cams
+
+    def mark(self, depth, cams, trunc):
+        """Flags the blocks that the truncation slabs of the depth pixels touch: depth (n,H,W) fp32 on the device, cams (n,16) on the
+        host as for integrate; any n, sixteen views to a launch."""
+        self._need(False, "mark")
+        n, H, W, cams = self._views(depth, cams, None, "mark")
+        grid, bdims = self._host()
+        for lo in range(0, n, MAX_VIEWS):
+            hi = min(lo + MAX_VIEWS, n)
+            _lib.call("rcmvs_tsdf_sp_mark", fusion._chk(depth[lo:hi], "depth"), hi - lo, H, W, cams[lo:hi].ctypes.data_as(ctypes.c_void_p), float(trunc),
+                      grid, bdims, fusion._chk(self.flags, "flags", torch.uint8), fusion._chk(self._skipped, "skipped", torch.int64), fusion._stream())
+        return self
+
+    def build(self):
+        """Fixes the block set from ``flags`` and allocates the planes -> the number of active blocks."""
+        self._need(False, "build")
+        dev, words = self.device, (self.blocks + 31) // 32
+        self.mask_words = torch.empty(words, device=dev, dtype=torch.int32)
+        self.word_rank = torch.empty(words + 1, device=dev, dtype=torch.int32)
+        active = torch.empty(min(self.blocks, SP_MAX_ACTIVE), device=dev, dtype=torch.int32)
+        work = torch.empty((words + SP_SCAN_TILE - 1) // SP_SCAN_TILE, device=dev, dtype=torch.int32)
+        _lib.call("rcmvs_tsdf_sp_build", fusion._chk(self.flags, "flags", torch.uint8), self._host()[1], fusion._chk(self.mask_words, "mask_words", torch.int32),
+                  fusion._chk(self.word_rank, "word_rank", torch.int32), fusion._chk(active, "active", torch.int32), int(active.numel()),
+                  fusion._chk(work, "scan_work", torch.int32), fusion._stream())
+        total = int(self.word_rank[words:].cpu()[0]) & 0xffffffff      # the one host synchronisation of a build
+        self.skipped = int(self._skipped.cpu()[0])
+        if total < 1 or total > SP_MAX_ACTIVE:
+            raise _lib.RcmvsError(f"SparseTsdfVolume.build: {total} active blocks of {self.blocks} (1 .. 2^19): " +
+                                  ("no depth sample falls into the grid" if total < 1 else "use larger voxels or tighter bounds"))
+        self.active = active[:total].contiguous()
+        self.n_active, self.voxels = total, total * SP_VOXELS
+        self.dsum = torch.zeros(self.voxels, device=dev, dtype=torch.float32)
+        self.wsum = torch.zeros(self.voxels, device=dev, dtype=torch.float32)
+        self.csum = [torch.zeros(self.voxels, device=dev, dtype=torch.float32) for _ in range(3)] if self.colour else None
+        return total
+
+    def integrate(self, depth, cams, rgb=None, trunc=None):
+        """As TsdfVolume.integrate, on the allocated voxels."""
+        self._need(True, "integrate")
+        if trunc is None:
+            raise _lib.RcmvsError("SparseTsdfVolume.integrate: trunc (the truncation distance, in world units) is required")
+        n, H, W, cams = self._views(depth, cams, rgb, "integrate")
+        grid, bdims = self._host()
+        for lo in range(0, n, MAX_VIEWS):
+            hi = min(lo + MAX_VIEWS, n)
+            _lib.call("rcmvs_tsdf_sp_integrate", fusion._chk(depth[lo:hi], "depth"), _ptr(None if rgb is None else rgb[lo:hi], "rgb", torch.uint8),
+                      hi - lo, H, W, cams[lo:hi].ctypes.data_as(ctypes.c_void_p), float(trunc), grid, bdims, fusion._chk(self.active, "active", torch.int32),
+                      self.n_active, fusion._chk(self.dsum, "dsum"), fusion._chk(self.wsum, "wsum"), *self._colour_ptrs(), fusion._stream())
+        return self
+
+    def count(self, min_weight=1):
+        """-> (edge_mask, tri_count (uint8 per allocated voxel), vert_start, tri_start (voxels + 1 int32), (vertices, faces) as ints)"""
+        self._need(True, "count")
+        dev, n = self.device, self.voxels
+        edge_mask = torch.empty(n, device=dev, dtype=torch.uint8)
+        tri_count = torch.empty(n, device=dev, dtype=torch.uint8)
+        work = torch.empty(1024 + 2 * self.n_active, device=dev, dtype=torch.int32)
+        vert_start = torch.empty(n + 1, device=dev, dtype=torch.int32)
+        tri_start = torch.empty(n + 1, device=dev, dtype=torch.int32)
+        totals = torch.empty(2, device=dev, dtype=torch.int64)
+        _lib.call("rcmvs_tsdf_sp_mesh_count", fusion._chk(self.dsum, "dsum"), fusion._chk(self.wsum, "wsum"), self._host()[1], *self._table(),
+                  int(min_weight), fusion._chk(edge_mask, "edge_mask", torch.uint8), fusion._chk(tri_count, "tri_count", torch.uint8),
+                  fusion._chk(work, "scan_work", torch.int32), fusion._chk(vert_start, "vert_start", torch.int32),
+                  fusion._chk(tri_start, "tri_start", torch.int32), fusion._chk(totals, "totals", torch.int64), fusion._stream())
+        nv, nf = (int(t) for t in totals.cpu())                      # the one host synchronisation of an extraction
+        return edge_mask, tri_count, vert_start, tri_start, (nv, nf)
+
+    def extract(self, min_weight=1):
+        """-> (verts (nv,3) fp32, faces (nf,3) int32, rgb (nv,3) uint8 or None without colour planes), device tensors, ordered by
+        the allocated voxel number"""
+        edge_mask, tri_count, vert_start, tri_start, (nv, nf) = self.count(min_weight)
+        if nv >= 1 << 31 or nf >= 1 << 31:
+            raise _lib.RcmvsError(f"SparseTsdfVolume.extract: {nv} vertices, {nf} faces (below 2^31 each): use larger voxels")
+        dev = self.device
+        verts = torch.empty((nv, 3), device=dev, dtype=torch.float32)
+        faces = torch.empty((nf, 3), device=dev, dtype=torch.int32)
+        rgb = torch.empty((nv, 3), device=dev, dtype=torch.uint8) if self.csum is not None else None
+        grid, bdims = self._host()
+        _lib.call("rcmvs_tsdf_sp_mesh_emit", fusion._chk(self.dsum, "dsum"), fusion._chk(self.wsum, "wsum"), *self._colour_ptrs(), grid, bdims,
+                  *self._table(), int(min_weight), fusion._chk(edge_mask, "edge_mask", torch.uint8), fusion._chk(tri_count, "tri_count", torch.uint8),
+                  fusion._chk(vert_start, "vert_start", torch.int32), fusion._chk(tri_start, "tri_start", torch.int32), nv, nf,
+                  _ptr(verts if nv else None, "verts", torch.float32), _ptr(rgb if nv else None, "vert_rgb", torch.uint8),
+                  _ptr(faces if nf else None, "faces", torch.int32), fusion._stream())
+        return verts, faces, rgb
+
+
 def mesh_ply_bytes(verts, faces, rgb=None):
     """Binary little-endian PLY of a triangle mesh: vertex properties x y z (float) red green blue (uchar), then ``element face``
     with ``property list uchar int vertex_indices``.  rgb None: white.  dtu_io.read_ply_mesh reads it back exactly."""
@@ -133,6 +271,21 @@ def camera_row(K, E):
     return np.concatenate([E[:3, :3].ravel(), E[:3, 3], [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]])
 
 
+def _add_view(r, cam, depths, colours, rows, lo, hi):
+    """one fuse_view result -> its depth_avg under the final mask, colours and camera row appended; -> the grown bounding box"""
+    keep = r["masks"][2] != 0
+    depths.append(torch.where(keep, r["depth_avg"], torch.zeros_like(r["depth_avg"])))
+    colours.append(r["rgb"])
+    rows.append(camera_row(*cam))
+    if bool(keep.any()):
+        pts = r["xyz"][keep].double()
+        pts = pts[torch.isfinite(pts).all(1)]
+        if len(pts):
+            a, b = pts.min(0).values.cpu().numpy(), pts.max(0).values.cpu().numpy()
+            lo, hi = (a, b) if lo is None else (np.minimum(lo, a), np.maximum(hi, b))
+    return lo, hi
+
+
 def filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage=3,
                    device="cuda:0"):
     """fusion.fuse_view per reference view of pair.txt, as filter_depth runs it -> dict: depth (V,H,W) fp32 = depth_avg where the
@@ -154,17 +307,69 @@ def filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_con
         mats = torch.from_numpy(fusion.fusion_matrices(cams[ref][0], cams[ref][1], [cams[s][0] for s in srcs], [cams[s][1] for s in srcs])).to(dev)
         r = fusion.fuse_view(depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, prob_threshold, num_consistent, img_dist_thresh,
                              depth_thresh)
-        keep = r["masks"][2] != 0
-        depths.append(torch.where(keep, r["depth_avg"], torch.zeros_like(r["depth_avg"])))
-        colours.append(r["rgb"])
-        rows.append(camera_row(*cams[ref]))
-        if bool(keep.any()):
-            pts = r["xyz"][keep].double()
-            pts = pts[torch.isfinite(pts).all(1)]
-            if len(pts):
-                a, b = pts.min(0).values.cpu().numpy(), pts.max(0).values.cpu().numpy()
-                lo, hi = (a, b) if lo is None else (np.minimum(lo, a), np.maximum(hi, b))
+        lo, hi = _add_view(r, cams[ref], depths, colours, rows, lo, hi)
     return {"depth": torch.stack(depths).contiguous(), "rgb": torch.stack(colours).contiguous(), "cams": np.stack(rows), "lo": lo, "hi": hi}
+
+
+def filtered_views_tanks(scan_folder, out_folder, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes, geo_mask_thres,
+                         device="cuda:0", depth_maps=None, conf_maps=None):
+    """filtered_views for a Tanks-and-Temples scene, as fusion.filter_depth_tanks runs the filter: cams_1/ with the intrinsics
+    rescaled to ``img_wh``, the image resized by prepare_image, depth_maps / conf_maps optionally still on the device."""
+    from PIL import Image
+    from .mvs_dataset import prepare_image
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    pairs = scan_io.read_pair_file(os.path.join(scan_folder, "pair.txt"))
+    views = sorted({v for ref, srcs in pairs for v in [ref] + list(srcs)})
+    slot = {v: i for i, v in enumerate(views)}
+    ow, oh = image_sizes
+    cams = {}
+    for v in views:
+        K, E = scan_io.read_camera_parameters(os.path.join(scan_folder, "cams_1/{:0>8}_cam.txt".format(v)))
+        K[0] *= img_wh[0] / ow
+        K[1] *= img_wh[1] / oh
+        cams[v] = (K, E)
+
+    def plane(maps, v, kind):
+        t = fusion._resident(maps, v, dev, kind)
+        if t is None:
+            t = torch.from_numpy(np.ascontiguousarray(read_pfm(os.path.join(out_folder, "{}/{:0>8}.pfm".format(kind, v)))[0])).to(dev)
+        return t
+
+    depth_all = torch.stack([plane(depth_maps, v, "depth_est") for v in views])
+    if tuple(depth_all.shape[1:]) != (img_wh[1], img_wh[0]):
+        raise _lib.RcmvsError(f"mesh_scan_tanks: depth maps are {tuple(depth_all.shape[1:])}, img_wh says {(img_wh[1], img_wh[0])}")
+    depths, colours, rows, lo, hi = [], [], [], None, None
+    for ref, srcs in pairs:
+        if len(srcs) > fusion.MAX_SRC:
+            raise _lib.RcmvsError(f"mesh_scan_tanks: view {ref} lists {len(srcs)} source views (at most {fusion.MAX_SRC})")
+        conf = plane(conf_maps, ref, "confidence")
+        raw = np.array(Image.open(os.path.join(scan_folder, "images/{:0>8}.jpg".format(ref))), dtype=np.uint8)
+        img = prepare_image(raw, (img_wh[1], img_wh[0]), dev, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)).permute(1, 2, 0).contiguous()
+        mats = torch.from_numpy(fusion.fusion_matrices(cams[ref][0], cams[ref][1], [cams[s][0] for s in srcs], [cams[s][1] for s in srcs])).to(dev)
+        r = fusion.fuse_view(depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, photo_thres, geo_mask_thres, geo_pixel_thres,
+                             geo_depth_thres)
+        lo, hi = _add_view(r, cams[ref], depths, colours, rows, lo, hi)
+    return {"depth": torch.stack(depths).contiguous(), "rgb": torch.stack(colours).contiguous(), "cams": np.stack(rows), "lo": lo, "hi": hi}
+
+
+def mesh_scan_tanks(scan_folder, out_folder, meshfilename, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes, geo_mask_thres,
+                    n_views=None, scan="", device="cuda:0", depth_maps=None, conf_maps=None, voxel=None, resolution=1024, trunc_voxels=3.0,
+                    min_weight=1, bounds=None):
+    """The mesh counterpart of fusion.filter_depth_tanks, with its arguments: the scene's filtered ``depth_avg`` maps integrated into
+    a SparseTsdfVolume (always sparse: these are the scenes a dense box does not fit) and meshed into ``meshfilename``.  Where no
+    point survives the filter and no bounds are given there is nothing to put a grid round: the PLY is written empty, as
+    filter_depth_tanks writes an empty cloud, and the summary says so."""
+    views = filtered_views_tanks(scan_folder, out_folder, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes, geo_mask_thres,
+                                 device, depth_maps, conf_maps)
+    if bounds is None and views["lo"] is None:
+        os.makedirs(os.path.dirname(os.path.abspath(meshfilename)), exist_ok=True)
+        with open(meshfilename, "wb") as f:
+            f.write(mesh_ply_bytes(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)))
+        return {"mesh": meshfilename, "views": int(views["depth"].shape[0]), "vertices": 0, "faces": 0, "active_blocks": 0, "allocated_voxels": 0,
+                "skipped_pixels": 0, "empty": "no point survives the filter"}
+    return _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, True, device)
 
 
 def plan_grid(lo, hi, voxel=None, resolution=256, trunc_voxels=3.0, pad=True):
@@ -187,30 +392,72 @@ def plan_grid(lo, hi, voxel=None, resolution=256, trunc_voxels=3.0, pad=True):
     return [float(v) for v in lo], voxel, dims, trunc
 
 
-def mesh_scan(pair_folder, scan_folder, out_folder, meshfilename, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage=3,
-              voxel=None, resolution=256, trunc_voxels=3.0, min_weight=1, bounds=None, device="cuda:0"):
-    """Mesh one scan laid out as fusion.filter_depth reads it into ``meshfilename``.  bounds: (xmin, ymin, zmin, xmax, ymax, zmax),
-    default the bounding box of the points that survive the filter, padded by the truncation distance.  Returns the summary dict."""
-    views = filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage, device)
+def plan_sparse_grid(lo, hi, voxel=None, resolution=1024, trunc_voxels=3.0, pad=True):
+    """plan_grid for a SparseTsdfVolume: the sides are rounded up to whole blocks of 8 voxels and the limit is 2^27 blocks, not
+    2^28 voxels -> (origin, voxel, bdims, trunc)."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all()):
+        raise _lib.RcmvsError(f"mesh_scan: bad bounds {lo} .. {hi}")
+    if voxel is None:
+        voxel = float((hi - lo).max()) / int(resolution)
+    voxel = float(voxel)
+    if not (math.isfinite(voxel) and voxel > 0 and math.isfinite(trunc_voxels) and trunc_voxels > 0):
+        raise _lib.RcmvsError(f"mesh_scan: voxel {voxel}, trunc_voxels {trunc_voxels} (finite, positive; a box without extent needs --voxel)")
+    trunc = float(trunc_voxels) * voxel
+    if pad:
+        lo, hi = lo - trunc, hi + trunc
+    sides = [float(s) / voxel for s in (hi - lo)]
+    if not all(s < 8.0 * SP_MAX_BLOCKS for s in sides):
+        raise _lib.RcmvsError(f"mesh_scan: voxels of {voxel} in a box of {hi - lo} (at most 2^27 blocks): use larger voxels or tighter bounds")
+    bdims = [max(1, (int(math.ceil(s)) + SP_BLOCK - 1) // SP_BLOCK) for s in sides]
+    if bdims[0] * bdims[1] * bdims[2] > SP_MAX_BLOCKS:
+        raise _lib.RcmvsError(f"mesh_scan: {bdims[0]} x {bdims[1]} x {bdims[2]} blocks of 8^3 voxels of {voxel} (at most 2^27): use larger voxels or "
+                              "tighter bounds")
+    return [float(v) for v in lo], voxel, bdims, trunc
+
+
+def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, sparse, device):
+    """Plans the grid, integrates the filtered views, extracts and writes the PLY -> the summary dict"""
+    plan = plan_sparse_grid if sparse else plan_grid
     if bounds is not None:
         b = [float(v) for v in bounds]
         if len(b) != 6:
             raise _lib.RcmvsError("mesh_scan: bounds are xmin ymin zmin xmax ymax zmax")
-        origin, voxel, dims, trunc = plan_grid(b[:3], b[3:], voxel, resolution, trunc_voxels, pad=False)
+        origin, voxel, dims, trunc = plan(b[:3], b[3:], voxel, resolution, trunc_voxels, pad=False)
     else:
         if views["lo"] is None:
             raise _lib.RcmvsError("mesh_scan: no point survives the filter, so there is no bounding box; give bounds")
-        origin, voxel, dims, trunc = plan_grid(views["lo"], views["hi"], voxel, resolution, trunc_voxels)
-    vol = TsdfVolume(origin, voxel, dims, device)
+        origin, voxel, dims, trunc = plan(views["lo"], views["hi"], voxel, resolution, trunc_voxels)
+    extra = {}
+    if sparse:
+        vol = SparseTsdfVolume(origin, voxel, dims, device)
+        vol.mark(views["depth"], views["cams"], trunc)
+        vol.build()
+        extra = {"bdims": dims, "active_blocks": vol.n_active, "allocated_voxels": vol.voxels, "skipped_pixels": vol.skipped}
+        dims = vol.dims
+    else:
+        vol = TsdfVolume(origin, voxel, dims, device)
     vol.integrate(views["depth"], views["cams"], views["rgb"], trunc=trunc)
     verts, faces, rgb = vol.extract(min_weight)
     os.makedirs(os.path.dirname(os.path.abspath(meshfilename)), exist_ok=True)
     with open(meshfilename, "wb") as f:
         f.write(mesh_ply_bytes(verts, faces, rgb))
     referenced = int(torch.unique(faces).numel())
-    return {"mesh": meshfilename, "origin": origin, "dims": dims, "voxel": voxel, "trunc": trunc, "min_weight": int(min_weight),
-            "views": int(views["depth"].shape[0]), "vertices": int(verts.shape[0]), "faces": int(faces.shape[0]),
-            "unreferenced_vertices": int(verts.shape[0]) - referenced, "observed_voxels": int((vol.wsum >= float(min_weight)).sum())}
+    return dict({"mesh": meshfilename, "origin": origin, "dims": dims, "voxel": voxel, "trunc": trunc, "min_weight": int(min_weight),
+                 "views": int(views["depth"].shape[0]), "vertices": int(verts.shape[0]), "faces": int(faces.shape[0]),
+                 "unreferenced_vertices": int(verts.shape[0]) - referenced, "observed_voxels": int((vol.wsum >= float(min_weight)).sum())}, **extra)
+
+
+def mesh_scan(pair_folder, scan_folder, out_folder, meshfilename, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage=3,
+              voxel=None, resolution=256, trunc_voxels=3.0, min_weight=1, bounds=None, device="cuda:0", sparse=False):
+    """Mesh one scan laid out as fusion.filter_depth reads it into ``meshfilename``.  bounds: (xmin, ymin, zmin, xmax, ymax, zmax),
+    default the bounding box of the points that survive the filter, padded by the truncation distance.  sparse: a SparseTsdfVolume
+    planned by plan_sparse_grid (resolution None: 1024); the summary then also reports bdims, active_blocks, allocated_voxels and
+    skipped_pixels.  Returns the summary dict."""
+    views = filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage, device)
+    if resolution is None:
+        resolution = 1024 if sparse else 256
+    return _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, bool(sparse), device)
 
 
 def main(argv=None):
@@ -225,7 +472,8 @@ def main(argv=None):
     ap.add_argument("--depth_thres", type=float, default=0.01)
     ap.add_argument("--num-stage", type=int, default=3)
     ap.add_argument("--voxel", type=float, default=None, help="voxel edge in world units (default: longest side / --resolution)")
-    ap.add_argument("--resolution", type=int, default=256)
+    ap.add_argument("--resolution", type=int, default=None, help="default 256, with --sparse 1024")
+    ap.add_argument("--sparse", action="store_true", help="a block-sparse volume: 8^3-voxel blocks allocated around the depth samples")
     ap.add_argument("--trunc-voxels", type=float, default=3.0, help="truncation distance in voxels")
     ap.add_argument("--min-weight", type=int, default=1, help="views a voxel must have been seen by")
     ap.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("XMIN", "YMIN", "ZMIN", "XMAX", "YMAX", "ZMAX"))
@@ -233,7 +481,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     summary = mesh_scan(a.pair_folder, a.scan_folder, a.out_folder, a.mesh, a.prob_thres, a.num_consistency, a.img_dist_thres, a.depth_thres,
                         num_stage=a.num_stage, voxel=a.voxel, resolution=a.resolution, trunc_voxels=a.trunc_voxels, min_weight=a.min_weight,
-                        bounds=a.bounds, device=a.device)
+                        bounds=a.bounds, device=a.device, sparse=a.sparse)
     print(json.dumps(summary))
     return summary
 
