@@ -126,7 +126,8 @@ def run_scans(model, args, device, rank, world):
                 summary = tsdf_mesh.mesh_scan(os.path.join(args.testpath, scan), folder, folder, os.path.join(args.outdir, scan + "_mesh.ply"),
                                               args.prob_thres, args.num_consistency, args.img_dist_thres, args.depth_thres, num_stage=nstage,
                                               voxel=args.mesh_voxel, resolution=args.mesh_resolution, trunc_voxels=args.mesh_trunc_voxels,
-                                              device=str(device), sparse=args.mesh_sparse)
+                                              device=str(device), sparse=args.mesh_sparse, min_faces=args.mesh_min_faces,
+                                              min_fraction=args.mesh_min_fraction, keep_largest=args.mesh_keep_largest, smooth=args.mesh_smooth)
                 print(json.dumps(summary))
             if args.dtu_gt:
                 score_scan(args, scan, device)
@@ -214,7 +215,9 @@ def run_tanks(model, args, device, rank, world):
                                                 os.path.join(args.plydir, scene + "_mesh.ply"), f["geo_pixel_thres"], f["geo_depth_thres"],
                                                 f["photo_thres"], img_wh, f["image_size"], f["geo_mask_thres"], args.num_view, scene,
                                                 device=str(device), depth_maps=depth_maps, conf_maps=conf_maps, voxel=args.mesh_voxel,
-                                                resolution=args.mesh_resolution or 1024, trunc_voxels=args.mesh_trunc_voxels)
+                                                resolution=args.mesh_resolution or 1024, trunc_voxels=args.mesh_trunc_voxels,
+                                                min_faces=args.mesh_min_faces, min_fraction=args.mesh_min_fraction,
+                                                keep_largest=args.mesh_keep_largest, smooth=args.mesh_smooth)
             print(json.dumps(summary))
         del depth_maps, conf_maps
     if times:
@@ -263,6 +266,10 @@ def main(argv=None):
                                                                       "(default 256; 1024 with --mesh-sparse and for tanks)")
     ap.add_argument("--mesh-sparse", action="store_true", help="--mesh: a block-sparse volume (tsdf_mesh.SparseTsdfVolume); tanks always uses it")
     ap.add_argument("--mesh-trunc-voxels", type=float, default=3.0, help="--mesh: truncation distance in voxels")
+    ap.add_argument("--mesh-min-faces", type=int, default=0, help="--mesh: clean-up (rc_mvsnet_amd.mesh_clean), drop components with fewer faces")
+    ap.add_argument("--mesh-min-fraction", type=float, default=0.0, help="--mesh: clean-up, drop components below this fraction of the largest one's faces")
+    ap.add_argument("--mesh-keep-largest", type=int, default=0, help="--mesh: clean-up, keep only the K components with most faces")
+    ap.add_argument("--mesh-smooth", type=int, default=0, help="--mesh: clean-up, rounds of Taubin smoothing")
     ap.add_argument("--dtu-gt", default=None, help="DTU MVS_Data folder: after --filter, score each fused cloud (accuracy / completeness, "
                                                    "rc_mvsnet_amd.dtu_eval)")
     ap.add_argument("--prob_thres", type=float, default=0.8)
