@@ -180,6 +180,22 @@ def read_ply_mesh(path):
     the first element plyread.m would take (face, Face, poly, Poly, tri, Tri) with its index list (vertex_indices,
     vertex_indexes, vertex_index, indices, indexes; any integer types); other properties are skipped.  No face element gives
     (0,3) faces.  Refused with FormatError: non-triangle faces, indices outside 0 .. n-1, non-finite vertices."""
+    return _read_ply_mesh(path, False)[:2]
+
+
+def read_ply_mesh_rgb(path):
+    """read_ply_mesh plus the vertex colours, in the same single pass -> (verts, faces, rgb (n,3) uint8 or None).  The colours are
+    the vertex element's red green blue (or r g b, or diffuse_red diffuse_green diffuse_blue) when all three are there as uchar;
+    anything else gives None."""
+    return _read_ply_mesh(path, True)
+
+
+_COLOUR_PROPS = (("red", "green", "blue"), ("r", "g", "b"), ("diffuse_red", "diffuse_green", "diffuse_blue"))
+
+
+def _read_ply_mesh(path, colours):
+    """the reader behind read_ply_mesh and read_ply_mesh_rgb -> (verts, faces, rgb or None); colours False: rgb is not looked for"""
+    rgb = None
     with open(path, "rb") as f:
         fmt, elements = _ply_header(f)
         names = [e[0] for e in elements]
@@ -193,6 +209,7 @@ def read_ply_mesh(path):
                 raise FormatError(f"{path}: vertex has no property {k}")
         if any(isinstance(t, tuple) for _, t in vprops):
             raise FormatError(f"{path}: list properties in the vertex element are not supported")
+        triple = next((t for t in _COLOUR_PROPS if all(k in pnames and np.dtype(vprops[pnames.index(k)][1]) == np.uint8 for k in t)), None) if colours else None
         idx = None
         if face_name is not None:
             fprops = elements[names.index(face_name)][2]
@@ -211,6 +228,9 @@ def read_ply_mesh(path):
                 if name == "vertex":
                     cols = [pnames.index(k) for k in ("x", "y", "z")]
                     verts = np.array([[float(r[c]) for c in cols] for r in rows], dtype=np.float64).astype(np.float32).reshape(count, 3)
+                    if triple is not None:
+                        cols = [pnames.index(k) for k in triple]
+                        rgb = np.array([[int(r[c]) for c in cols] for r in rows], dtype=np.uint8).reshape(count, 3)
                 elif name == face_name:
                     bad = next((r for r, row in enumerate(rows) if len(row[idx]) != 3), None)
                     if bad is not None:
@@ -227,6 +247,8 @@ def read_ply_mesh(path):
                         raise FormatError(f"{path}: truncated vertex data")
                     rec = np.frombuffer(buf, dtype=dt)
                     verts = np.stack([rec[k].astype(np.float32) for k in ("x", "y", "z")], axis=1).reshape(count, 3)
+                    if triple is not None:
+                        rgb = np.stack([rec[k] for k in triple], axis=1).astype(np.uint8).reshape(count, 3)
                     done += 1
                 elif name == face_name:
                     faces = _binary_faces(f, count, props, idx, end, path)
@@ -240,7 +262,7 @@ def read_ply_mesh(path):
     n = len(verts)
     if len(faces) and (faces.min() < 0 or faces.max() >= n):
         raise FormatError(f"{path}: face indices outside 0 .. {n - 1}")
-    return verts, faces.astype(np.int32).reshape(-1, 3)
+    return verts, faces.astype(np.int32).reshape(-1, 3), rgb
 
 
 # ---- MAT v5 --------------------------------------------------------------------------------------------------------------

@@ -127,7 +127,8 @@ def run_scans(model, args, device, rank, world):
                                               args.prob_thres, args.num_consistency, args.img_dist_thres, args.depth_thres, num_stage=nstage,
                                               voxel=args.mesh_voxel, resolution=args.mesh_resolution, trunc_voxels=args.mesh_trunc_voxels,
                                               device=str(device), sparse=args.mesh_sparse, min_faces=args.mesh_min_faces,
-                                              min_fraction=args.mesh_min_fraction, keep_largest=args.mesh_keep_largest, smooth=args.mesh_smooth)
+                                              min_fraction=args.mesh_min_fraction, keep_largest=args.mesh_keep_largest, smooth=args.mesh_smooth,
+                                              decimate_voxels=args.mesh_decimate_voxels)
                 print(json.dumps(summary))
             if args.dtu_gt:
                 score_scan(args, scan, device)
@@ -217,7 +218,8 @@ def run_tanks(model, args, device, rank, world):
                                                 device=str(device), depth_maps=depth_maps, conf_maps=conf_maps, voxel=args.mesh_voxel,
                                                 resolution=args.mesh_resolution or 1024, trunc_voxels=args.mesh_trunc_voxels,
                                                 min_faces=args.mesh_min_faces, min_fraction=args.mesh_min_fraction,
-                                                keep_largest=args.mesh_keep_largest, smooth=args.mesh_smooth)
+                                                keep_largest=args.mesh_keep_largest, smooth=args.mesh_smooth,
+                                                decimate_voxels=args.mesh_decimate_voxels)
             print(json.dumps(summary))
         del depth_maps, conf_maps
     if times:
@@ -270,6 +272,8 @@ def main(argv=None):
     ap.add_argument("--mesh-min-fraction", type=float, default=0.0, help="--mesh: clean-up, drop components below this fraction of the largest one's faces")
     ap.add_argument("--mesh-keep-largest", type=int, default=0, help="--mesh: clean-up, keep only the K components with most faces")
     ap.add_argument("--mesh-smooth", type=int, default=0, help="--mesh: clean-up, rounds of Taubin smoothing")
+    ap.add_argument("--mesh-decimate-voxels", type=float, default=0.0,
+                    help="--mesh: decimation (rc_mvsnet_amd.mesh_decimate) after the clean-up, cells of this many voxels")
     ap.add_argument("--dtu-gt", default=None, help="DTU MVS_Data folder: after --filter, score each fused cloud (accuracy / completeness, "
                                                    "rc_mvsnet_amd.dtu_eval)")
     ap.add_argument("--prob_thres", type=float, default=0.8)

@@ -12,8 +12,8 @@ neighbours are ascending, and a smoothing step sums them in that order in fp64. 
 
 Limits: connectivity is over vertices (two faces that share a vertex are one component); at most 2^31 - 1 directed 1-ring
 entries, i.e. 357 913 941 faces; a vertex with more than 48 entries is sorted by a slower path whose time grows with the square
-of its degree; the command line reads positions and faces only, so it writes white vertices.  No hole filling or decimation.  No
-CPU fallback."""
+of its degree; the command line reads positions and faces only, so it writes white vertices.  No hole filling; decimation is
+rc_mvsnet_amd.mesh_decimate's.  No CPU fallback."""
 import argparse
 import ctypes
 import json
