@@ -12,8 +12,8 @@ neighbours are ascending, and a smoothing step sums them in that order in fp64. 
 
 Limits: connectivity is over vertices (two faces that share a vertex are one component); at most 2^31 - 1 directed 1-ring
 entries, i.e. 357 913 941 faces; a vertex with more than 48 entries is sorted by a slower path whose time grows with the square
-of its degree; the command line reads positions and faces only, so it writes white vertices.  No hole filling; decimation is
-rc_mvsnet_amd.mesh_decimate's.  No CPU fallback."""
+of its degree; the command line reads positions and faces only, so it writes white vertices.  Hole filling (``fill_holes``) is
+rc_mvsnet_amd.mesh_holes', decimation rc_mvsnet_amd.mesh_decimate's.  No CPU fallback."""
 import argparse
 import ctypes
 import json
@@ -201,36 +201,50 @@ def taubin(verts, adj, iterations=10, lam=0.5, mu=-0.53, pin_boundary=True):
 
 
 def clean_mesh(verts, faces, rgb=None, *, min_faces=0, min_fraction=0.0, keep_largest=0, drop_unreferenced=True, smooth_iterations=0, lam=0.5,
-               mu=-0.53, pin_boundary=True):
+               mu=-0.53, pin_boundary=True, fill_holes=0):
     """Removes invalid faces and the components the three rules reject (faces >= min_faces; faces >= min_fraction * the largest
     component's; among the keep_largest largest, ties to the smaller label; the defaults keep everything), drops the vertices no
-    kept face uses (drop_unreferenced), then runs smooth_iterations rounds of Taubin smoothing -> (verts, faces, rgb, stats)."""
+    kept face uses (drop_unreferenced), closes the boundary loops of at most fill_holes edges (mesh_holes.fill_holes; 0: none, and
+    nothing new runs), then runs smooth_iterations rounds of Taubin smoothing on the filled mesh, whose 1-ring and counts the stats
+    describe -> (verts, faces, rgb, stats); with fill_holes, stats["holes"] are mesh_holes' counts."""
     what = "mesh_clean.clean_mesh"
     nv, nf = _mesh(verts, faces, rgb, what)
     for name, value in (("min_faces", min_faces), ("keep_largest", keep_largest)):
         _count(value, name, what)
     smooth_iterations = _count(smooth_iterations, "smooth_iterations", what)
+    if _count(fill_holes, "fill_holes", what):
+        from . import mesh_holes
+        fill_holes = mesh_holes.max_edges_argument(fill_holes, what)
     for name, value in (("min_fraction", min_fraction), ("lam", lam), ("mu", mu)):
         _real(value, name, what)
     comp = components(verts, faces)
     v, f, c, info = compact(verts, faces, rgb, comp, min_faces=min_faces, min_fraction=min_fraction, keep_largest=keep_largest,
                             drop_unreferenced=drop_unreferenced)
+    holes = None
+    if fill_holes:
+        v, f, c, holes = mesh_holes.fill_holes(v, f, c, max_edges=fill_holes)
     adj = adjacency(int(v.shape[0]), f)
     if smooth_iterations:
         v = taubin(v, adj, smooth_iterations, lam, mu, pin_boundary)
     stats = {"vertices_in": nv, "vertices_out": int(v.shape[0]), "faces_in": nf, "faces_out": int(f.shape[0]),
              "invalid_faces": int(comp["counts"][:1].cpu()[0]), "components_in": info["components_in"], "components_kept": info["components_kept"],
-             "largest_component_faces": info["largest_component_faces"], "unreferenced_removed": nv - int(v.shape[0]), "edges": adj["edges"],
+             "largest_component_faces": info["largest_component_faces"], "unreferenced_removed": nv - info["vertices_out"], "edges": adj["edges"],
              "boundary_edges": adj["boundary_edges"], "nonmanifold_edges": adj["nonmanifold_edges"],
              "euler_characteristic": adj["referenced_vertices"] - adj["edges"] + int(f.shape[0]), "smooth_iterations": smooth_iterations}
+    if holes is not None:
+        stats["holes"] = holes
     return v, f, c, stats
 
 
-def clean_options(min_faces=0, min_fraction=0.0, keep_largest=0, smooth=0):
-    """The mesh path's four options -> the keyword arguments of clean_mesh, or None when none of them asks for anything"""
-    if not (min_faces or min_fraction or keep_largest or smooth):
+def clean_options(min_faces=0, min_fraction=0.0, keep_largest=0, smooth=0, fill_holes=0):
+    """The mesh path's five options -> the keyword arguments of clean_mesh, or None when none of them asks for anything;
+    fill_holes is among them only when it is not 0"""
+    if not (min_faces or min_fraction or keep_largest or smooth or fill_holes):
         return None
-    return {"min_faces": min_faces, "min_fraction": min_fraction, "keep_largest": keep_largest, "smooth_iterations": smooth}
+    options = {"min_faces": min_faces, "min_fraction": min_fraction, "keep_largest": keep_largest, "smooth_iterations": smooth}
+    if fill_holes:
+        options["fill_holes"] = fill_holes
+    return options
 
 
 def main(argv=None):
@@ -242,6 +256,7 @@ def main(argv=None):
     ap.add_argument("--min-fraction", type=float, default=0.0, help="drop components with fewer than this fraction of the largest one's faces")
     ap.add_argument("--keep-largest", type=int, default=0, help="keep only the K components with most faces (0: no limit)")
     ap.add_argument("--smooth", type=int, default=0, help="rounds of Taubin smoothing")
+    ap.add_argument("--fill-holes", type=int, default=0, help="close boundary loops of at most N edges (3 .. 4096) before smoothing; 0: none")
     ap.add_argument("--lambda", dest="lam", type=float, default=0.5)
     ap.add_argument("--mu", type=float, default=-0.53)
     ap.add_argument("--no-pin-boundary", action="store_true", help="also move vertices on boundary edges")
@@ -253,7 +268,7 @@ def main(argv=None):
     v, f, _, stats = clean_mesh(torch.from_numpy(np.ascontiguousarray(verts, np.float32)).to(dev), torch.from_numpy(np.ascontiguousarray(faces, np.int32)).to(dev),
                                 None, min_faces=a.min_faces, min_fraction=a.min_fraction, keep_largest=a.keep_largest,
                                 drop_unreferenced=not a.keep_unreferenced, smooth_iterations=a.smooth, lam=a.lam, mu=a.mu,
-                                pin_boundary=not a.no_pin_boundary)
+                                pin_boundary=not a.no_pin_boundary, fill_holes=a.fill_holes)
     with open(a.out, "wb") as out:
         out.write(tsdf_mesh.mesh_ply_bytes(v, f, None))
     summary = dict({"in": a.src, "out": a.out}, **stats)

@@ -15,7 +15,7 @@ there is no per-vertex or per-face host pass.
 
 Limits: no feature-preserving edge collapse (one vertex per occupied cell, so two sheets closer than a cell merge and thin parts
 can collapse); clustering can create non-manifold edges, which the stats count; at most 2^21 cells per axis; at most 2^31 - 256
-vertices and (2^31 - 256) / 3 faces.  No hole filling.  No CPU fallback."""
+vertices and (2^31 - 256) / 3 faces.  No CPU fallback."""
 import argparse
 import ctypes
 import json

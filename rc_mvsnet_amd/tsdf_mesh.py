@@ -15,13 +15,14 @@ and ``mesh_scan_tanks`` use it.
 
 Limits: both volumes are axis-aligned.  The dense grid has at most 2^28 voxels; the sparse one at most 2^27 blocks (4096^3 voxels) of
 which at most 2^19 are active, its block set does not grow after build(), and a pixel whose slab spans more than 4 blocks on an
-axis is skipped and counted (with any skipped pixel the equality with the dense mesh is no longer guaranteed).  No hole filling;
-decimation is rc_mvsnet_amd.mesh_decimate's (``decimate_cell`` / ``decimate_voxels``); marching tetrahedra emits roughly twice the
+axis is skipped and counted (with any skipped pixel the equality with the dense mesh is no longer guaranteed).  Hole filling is
+rc_mvsnet_amd.mesh_holes' (``fill_holes``), decimation rc_mvsnet_amd.mesh_decimate's (``decimate_cell`` / ``decimate_voxels``); marching tetrahedra emits roughly twice the
 triangles of marching cubes; as extracted, the mesh carries floating
 fragments and vertices at the rim of the observed region that no face uses.  No CPU fallback.
 
-``min_faces`` / ``min_fraction`` / ``keep_largest`` / ``smooth`` (``--min-faces`` ...) run rc_mvsnet_amd.mesh_clean.clean_mesh between
-the extraction and the write: small components and unreferenced vertices removed, Taubin smoothing.  With none of them given
+``min_faces`` / ``min_fraction`` / ``keep_largest`` / ``smooth`` / ``fill_holes`` (``--min-faces`` ...) run rc_mvsnet_amd.mesh_clean.clean_mesh
+between the extraction and the write: small components and unreferenced vertices removed, boundary loops of at most ``fill_holes``
+edges closed, Taubin smoothing.  With none of them given
 nothing of it runs and the PLY and the summary are what they were."""
 import argparse
 import ctypes
@@ -361,7 +362,7 @@ def filtered_views_tanks(scan_folder, out_folder, geo_pixel_thres, geo_depth_thr
 
 def mesh_scan_tanks(scan_folder, out_folder, meshfilename, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes, geo_mask_thres,
                     n_views=None, scan="", device="cuda:0", depth_maps=None, conf_maps=None, voxel=None, resolution=1024, trunc_voxels=3.0,
-                    min_weight=1, bounds=None, min_faces=0, min_fraction=0.0, keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0):
+                    min_weight=1, bounds=None, min_faces=0, min_fraction=0.0, keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0):
     """The mesh counterpart of fusion.filter_depth_tanks, with its arguments: the scene's filtered ``depth_avg`` maps integrated into
     a SparseTsdfVolume (always sparse: these are the scenes a dense box does not fit) and meshed into ``meshfilename``.  Where no
     point survives the filter and no bounds are given there is nothing to put a grid round: the PLY is written empty, as
@@ -375,7 +376,7 @@ def mesh_scan_tanks(scan_folder, out_folder, meshfilename, geo_pixel_thres, geo_
         return {"mesh": meshfilename, "views": int(views["depth"].shape[0]), "vertices": 0, "faces": 0, "active_blocks": 0, "allocated_voxels": 0,
                 "skipped_pixels": 0, "empty": "no point survives the filter"}
     return _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, True, device,
-                       mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth), **_decimate_argument(decimate_cell, decimate_voxels))
+                       mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth, fill_holes), **_decimate_argument(decimate_cell, decimate_voxels))
 
 
 def _decimate_argument(cell, voxels):
@@ -470,18 +471,18 @@ def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight
 
 def mesh_scan(pair_folder, scan_folder, out_folder, meshfilename, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage=3,
               voxel=None, resolution=256, trunc_voxels=3.0, min_weight=1, bounds=None, device="cuda:0", sparse=False, min_faces=0, min_fraction=0.0,
-              keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0):
+              keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0):
     """Mesh one scan laid out as fusion.filter_depth reads it into ``meshfilename``.  bounds: (xmin, ymin, zmin, xmax, ymax, zmax),
     default the bounding box of the points that survive the filter, padded by the truncation distance.  sparse: a SparseTsdfVolume
     planned by plan_sparse_grid (resolution None: 1024); the summary then also reports bdims, active_blocks, allocated_voxels and
-    skipped_pixels.  min_faces, min_fraction, keep_largest, smooth: any of them given, mesh_clean.clean_mesh runs on the extracted
-    mesh and the summary gains its stats as "clean".  decimate_cell (world units) or decimate_voxels (in voxels of the volume), not
+    skipped_pixels.  min_faces, min_fraction, keep_largest, smooth, fill_holes: any of them given, mesh_clean.clean_mesh runs on the
+    extracted mesh and the summary gains its stats as "clean" (with fill_holes, "holes" among them).  decimate_cell (world units) or decimate_voxels (in voxels of the volume), not
     both: mesh_decimate.decimate runs after the clean-up and the summary gains its stats as "decimate".  Returns the summary dict."""
     views = filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage, device)
     if resolution is None:
         resolution = 1024 if sparse else 256
     return _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, bool(sparse), device,
-                       mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth), **_decimate_argument(decimate_cell, decimate_voxels))
+                       mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth, fill_holes), **_decimate_argument(decimate_cell, decimate_voxels))
 
 
 def main(argv=None):
@@ -505,6 +506,7 @@ def main(argv=None):
     ap.add_argument("--min-fraction", type=float, default=0.0, help="clean-up: drop components below this fraction of the largest one's faces")
     ap.add_argument("--keep-largest", type=int, default=0, help="clean-up: keep only the K components with most faces")
     ap.add_argument("--smooth", type=int, default=0, help="clean-up: rounds of Taubin smoothing")
+    ap.add_argument("--fill-holes", type=int, default=0, help="clean-up: close boundary loops of at most N edges (rc_mvsnet_amd.mesh_holes; 0: none)")
     dec = ap.add_mutually_exclusive_group()
     dec.add_argument("--decimate-cell", type=float, default=0.0, help="decimation: edge of the clustering cells, world units")
     dec.add_argument("--decimate-voxels", type=float, default=0.0, help="decimation: edge of the clustering cells in voxels of the volume")
@@ -513,7 +515,8 @@ def main(argv=None):
     summary = mesh_scan(a.pair_folder, a.scan_folder, a.out_folder, a.mesh, a.prob_thres, a.num_consistency, a.img_dist_thres, a.depth_thres,
                         num_stage=a.num_stage, voxel=a.voxel, resolution=a.resolution, trunc_voxels=a.trunc_voxels, min_weight=a.min_weight,
                         bounds=a.bounds, device=a.device, sparse=a.sparse, min_faces=a.min_faces, min_fraction=a.min_fraction,
-                        keep_largest=a.keep_largest, smooth=a.smooth, decimate_cell=a.decimate_cell, decimate_voxels=a.decimate_voxels)
+                        keep_largest=a.keep_largest, smooth=a.smooth, decimate_cell=a.decimate_cell, decimate_voxels=a.decimate_voxels,
+                        fill_holes=a.fill_holes)
     print(json.dumps(summary))
     return summary
 
