@@ -128,7 +128,8 @@ def run_scans(model, args, device, rank, world):
                                               voxel=args.mesh_voxel, resolution=args.mesh_resolution, trunc_voxels=args.mesh_trunc_voxels,
                                               device=str(device), sparse=args.mesh_sparse, min_faces=args.mesh_min_faces,
                                               min_fraction=args.mesh_min_fraction, keep_largest=args.mesh_keep_largest, smooth=args.mesh_smooth,
-                                              decimate_voxels=args.mesh_decimate_voxels, fill_holes=args.mesh_fill_holes)
+                                              decimate_voxels=args.mesh_decimate_voxels, fill_holes=args.mesh_fill_holes,
+                                              render_dir=None if args.mesh_render is None else os.path.join(args.mesh_render, scan))
                 print(json.dumps(summary))
             if args.dtu_gt:
                 score_scan(args, scan, device)
@@ -219,7 +220,8 @@ def run_tanks(model, args, device, rank, world):
                                                 resolution=args.mesh_resolution or 1024, trunc_voxels=args.mesh_trunc_voxels,
                                                 min_faces=args.mesh_min_faces, min_fraction=args.mesh_min_fraction,
                                                 keep_largest=args.mesh_keep_largest, smooth=args.mesh_smooth,
-                                                decimate_voxels=args.mesh_decimate_voxels, fill_holes=args.mesh_fill_holes)
+                                                decimate_voxels=args.mesh_decimate_voxels, fill_holes=args.mesh_fill_holes,
+                                                render_dir=None if args.mesh_render is None else os.path.join(args.mesh_render, scene))
             print(json.dumps(summary))
         del depth_maps, conf_maps
     if times:
@@ -274,6 +276,9 @@ def main(argv=None):
     ap.add_argument("--mesh-smooth", type=int, default=0, help="--mesh: clean-up, rounds of Taubin smoothing")
     ap.add_argument("--mesh-fill-holes", type=int, default=0,
                     help="--mesh: clean-up, close boundary loops of at most N edges (rc_mvsnet_amd.mesh_holes) before the smoothing")
+    ap.add_argument("--mesh-render", default=None, metavar="DIR",
+                    help="--mesh: render each written mesh into the views it was fused from (rc_mvsnet_amd.mesh_render) under DIR/<scan> and add the "
+                         "comparison with the filtered depth maps to the summary as \"render\"")
     ap.add_argument("--mesh-decimate-voxels", type=float, default=0.0,
                     help="--mesh: decimation (rc_mvsnet_amd.mesh_decimate) after the clean-up, cells of this many voxels")
     ap.add_argument("--dtu-gt", default=None, help="DTU MVS_Data folder: after --filter, score each fused cloud (accuracy / completeness, "

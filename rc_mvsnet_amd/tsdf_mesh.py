@@ -23,7 +23,11 @@ fragments and vertices at the rim of the observed region that no face uses.  No 
 ``min_faces`` / ``min_fraction`` / ``keep_largest`` / ``smooth`` / ``fill_holes`` (``--min-faces`` ...) run rc_mvsnet_amd.mesh_clean.clean_mesh
 between the extraction and the write: small components and unreferenced vertices removed, boundary loops of at most ``fill_holes``
 edges closed, Taubin smoothing.  With none of them given
-nothing of it runs and the PLY and the summary are what they were."""
+nothing of it runs and the PLY and the summary are what they were.
+
+``render_dir`` (``--render DIR``) renders the mesh just written into the views it was fused from (rc_mvsnet_amd.mesh_render), writes
+their depth PFMs and shade / colour PNGs under that folder, compares the rendered depth with the filtered depth maps still on the
+device and adds the summed table to the summary as "render".  Without it nothing of it runs."""
 import argparse
 import ctypes
 import json
@@ -296,7 +300,7 @@ def filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_con
                    device="cuda:0"):
     """fusion.fuse_view per reference view of pair.txt, as filter_depth runs it -> dict: depth (V,H,W) fp32 = depth_avg where the
     final mask holds and 0 elsewhere, rgb (V,H,W,3) uint8, both on the device; cams (V,16) float64; lo, hi: the bounding box of
-    the surviving points (float64, None when no point survives)."""
+    the surviving points (float64, None when no point survives); ids: the V reference views' numbers in pair.txt's order."""
     dev = torch.device(device)
     pairs = scan_io.read_pair_file(os.path.join(pair_folder, "pair.txt"))
     views = sorted({v for ref, srcs in pairs for v in [ref] + list(srcs)})
@@ -314,7 +318,8 @@ def filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_con
         r = fusion.fuse_view(depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, prob_threshold, num_consistent, img_dist_thresh,
                              depth_thresh)
         lo, hi = _add_view(r, cams[ref], depths, colours, rows, lo, hi)
-    return {"depth": torch.stack(depths).contiguous(), "rgb": torch.stack(colours).contiguous(), "cams": np.stack(rows), "lo": lo, "hi": hi}
+    return {"depth": torch.stack(depths).contiguous(), "rgb": torch.stack(colours).contiguous(), "cams": np.stack(rows), "lo": lo, "hi": hi,
+            "ids": [int(ref) for ref, _ in pairs]}
 
 
 def filtered_views_tanks(scan_folder, out_folder, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes, geo_mask_thres,
@@ -357,12 +362,14 @@ def filtered_views_tanks(scan_folder, out_folder, geo_pixel_thres, geo_depth_thr
         r = fusion.fuse_view(depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, photo_thres, geo_mask_thres, geo_pixel_thres,
                              geo_depth_thres)
         lo, hi = _add_view(r, cams[ref], depths, colours, rows, lo, hi)
-    return {"depth": torch.stack(depths).contiguous(), "rgb": torch.stack(colours).contiguous(), "cams": np.stack(rows), "lo": lo, "hi": hi}
+    return {"depth": torch.stack(depths).contiguous(), "rgb": torch.stack(colours).contiguous(), "cams": np.stack(rows), "lo": lo, "hi": hi,
+            "ids": [int(ref) for ref, _ in pairs]}
 
 
 def mesh_scan_tanks(scan_folder, out_folder, meshfilename, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes, geo_mask_thres,
                     n_views=None, scan="", device="cuda:0", depth_maps=None, conf_maps=None, voxel=None, resolution=1024, trunc_voxels=3.0,
-                    min_weight=1, bounds=None, min_faces=0, min_fraction=0.0, keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0):
+                    min_weight=1, bounds=None, min_faces=0, min_fraction=0.0, keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0,
+                    render_dir=None):
     """The mesh counterpart of fusion.filter_depth_tanks, with its arguments: the scene's filtered ``depth_avg`` maps integrated into
     a SparseTsdfVolume (always sparse: these are the scenes a dense box does not fit) and meshed into ``meshfilename``.  Where no
     point survives the filter and no bounds are given there is nothing to put a grid round: the PLY is written empty, as
@@ -376,13 +383,19 @@ def mesh_scan_tanks(scan_folder, out_folder, meshfilename, geo_pixel_thres, geo_
         return {"mesh": meshfilename, "views": int(views["depth"].shape[0]), "vertices": 0, "faces": 0, "active_blocks": 0, "allocated_voxels": 0,
                 "skipped_pixels": 0, "empty": "no point survives the filter"}
     return _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, True, device,
-                       mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth, fill_holes), **_decimate_argument(decimate_cell, decimate_voxels))
+                       mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth, fill_holes), **_decimate_argument(decimate_cell, decimate_voxels),
+                       **_render_argument(render_dir))
 
 
 def _decimate_argument(cell, voxels):
     """-> the keyword that hands mesh_decimate.decimate_options to _mesh_views; nothing at all when neither option is given"""
     options = mesh_decimate.decimate_options(cell, voxels)
     return {} if options is None else {"decimate": options}
+
+
+def _render_argument(render_dir):
+    """-> the keyword that hands the folder of the rendered views to _mesh_views; nothing at all without one"""
+    return {} if render_dir is None else {"render": str(render_dir)}
 
 
 def plan_grid(lo, hi, voxel=None, resolution=256, trunc_voxels=3.0, pad=True):
@@ -429,10 +442,11 @@ def plan_sparse_grid(lo, hi, voxel=None, resolution=1024, trunc_voxels=3.0, pad=
     return [float(v) for v in lo], voxel, bdims, trunc
 
 
-def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, sparse, device, clean=None, decimate=None):
+def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, sparse, device, clean=None, decimate=None, render=None):
     """Plans the grid, integrates the filtered views, extracts, cleans the mesh when ``clean`` (the keyword arguments of
     mesh_clean.clean_mesh) is given, then decimates it when ``decimate`` (of mesh_decimate.decimate_options) is given, and writes
-    the PLY -> the summary dict"""
+    the PLY; with ``render`` (a folder) renders the written mesh into the views it was fused from (rc_mvsnet_amd.mesh_render) and
+    compares it with their filtered depth maps -> the summary dict"""
     plan = plan_sparse_grid if sparse else plan_grid
     if bounds is not None:
         b = [float(v) for v in bounds]
@@ -463,6 +477,9 @@ def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight
     os.makedirs(os.path.dirname(os.path.abspath(meshfilename)), exist_ok=True)
     with open(meshfilename, "wb") as f:
         f.write(mesh_ply_bytes(verts, faces, rgb))
+    if render is not None:
+        from . import mesh_render
+        extra["render"] = mesh_render.render_views(verts, faces, rgb, views, render)
     referenced = int(torch.unique(faces).numel())
     return dict({"mesh": meshfilename, "origin": origin, "dims": dims, "voxel": voxel, "trunc": trunc, "min_weight": int(min_weight),
                  "views": int(views["depth"].shape[0]), "vertices": int(verts.shape[0]), "faces": int(faces.shape[0]),
@@ -471,18 +488,21 @@ def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight
 
 def mesh_scan(pair_folder, scan_folder, out_folder, meshfilename, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage=3,
               voxel=None, resolution=256, trunc_voxels=3.0, min_weight=1, bounds=None, device="cuda:0", sparse=False, min_faces=0, min_fraction=0.0,
-              keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0):
+              keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0, render_dir=None):
     """Mesh one scan laid out as fusion.filter_depth reads it into ``meshfilename``.  bounds: (xmin, ymin, zmin, xmax, ymax, zmax),
     default the bounding box of the points that survive the filter, padded by the truncation distance.  sparse: a SparseTsdfVolume
     planned by plan_sparse_grid (resolution None: 1024); the summary then also reports bdims, active_blocks, allocated_voxels and
     skipped_pixels.  min_faces, min_fraction, keep_largest, smooth, fill_holes: any of them given, mesh_clean.clean_mesh runs on the
     extracted mesh and the summary gains its stats as "clean" (with fill_holes, "holes" among them).  decimate_cell (world units) or decimate_voxels (in voxels of the volume), not
-    both: mesh_decimate.decimate runs after the clean-up and the summary gains its stats as "decimate".  Returns the summary dict."""
+    both: mesh_decimate.decimate runs after the clean-up and the summary gains its stats as "decimate".  render_dir: the written mesh is
+    rendered into the views it was fused from (mesh_render.render_views: depth_mesh/ and render/ under that folder) and compared with
+    their filtered depth maps; the summary gains the summed table as "render".  Returns the summary dict."""
     views = filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage, device)
     if resolution is None:
         resolution = 1024 if sparse else 256
     return _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, bool(sparse), device,
-                       mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth, fill_holes), **_decimate_argument(decimate_cell, decimate_voxels))
+                       mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth, fill_holes), **_decimate_argument(decimate_cell, decimate_voxels),
+                       **_render_argument(render_dir))
 
 
 def main(argv=None):
@@ -510,13 +530,15 @@ def main(argv=None):
     dec = ap.add_mutually_exclusive_group()
     dec.add_argument("--decimate-cell", type=float, default=0.0, help="decimation: edge of the clustering cells, world units")
     dec.add_argument("--decimate-voxels", type=float, default=0.0, help="decimation: edge of the clustering cells in voxels of the volume")
+    ap.add_argument("--render", default=None, metavar="DIR", help="render the written mesh into the views it was fused from (rc_mvsnet_amd.mesh_render): "
+                                                                  "DIR/depth_mesh/*.pfm, DIR/render/*.png, and \"render\" in the summary")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     summary = mesh_scan(a.pair_folder, a.scan_folder, a.out_folder, a.mesh, a.prob_thres, a.num_consistency, a.img_dist_thres, a.depth_thres,
                         num_stage=a.num_stage, voxel=a.voxel, resolution=a.resolution, trunc_voxels=a.trunc_voxels, min_weight=a.min_weight,
                         bounds=a.bounds, device=a.device, sparse=a.sparse, min_faces=a.min_faces, min_fraction=a.min_fraction,
                         keep_largest=a.keep_largest, smooth=a.smooth, decimate_cell=a.decimate_cell, decimate_voxels=a.decimate_voxels,
-                        fill_holes=a.fill_holes)
+                        fill_holes=a.fill_holes, render_dir=a.render)
     print(json.dumps(summary))
     return summary
 
