@@ -5,9 +5,9 @@
 //               under the smaller by atomicCAS, halving the paths it walks; a flatten pass then writes every vertex's root, which
 //               is the smallest vertex of its component whatever the order of the hooks was (DESIGN.md has the argument).  No
 //               thread waits for another: a failed CAS means another hook succeeded, and the retry starts strictly lower.
-//   scan        Flags or counts -> exclusive prefix sums in three levels: tiles of 2048, 2048 tile sums, at most 1024 top sums
-//               by one thread; 64-bit above the tile level.  Used for the component table, the kept faces, the kept vertices
-//               and the 1-ring's row starts.
+//   scan        Flags or counts -> exclusive prefix sums in three levels: scan_sort.hip's scan3, which mesh_decimate.hip and
+//               mesh_holes.hip call too.  Used for the component table, the kept faces, the kept vertices and the 1-ring's
+//               row starts.
 //   select      Per face the keep rule of its first index's component; kept faces mark their vertices with plain byte stores of 1.
 //   gather      Kept vertices and faces to their ranks: stable, bit copies, indices rewritten through the vertex rank.
 //   adjacency   Entry counts by atomicAdd, scan, fill through the same counters counting down (arbitrary order inside a segment),
@@ -21,101 +21,23 @@
 #include "common.h"
 #include "mesh_clean.h"
 #include "mesh_clean_math.h"
-#include "tsdf_mesh_cells.h"                                      // tm_block_sum, tm_block_exclusive (256 threads)
+#include "scan_sort.h"                                            // scan3, zero_u64_kernel
+#include "tsdf_mesh_cells.h"                                      // tm_block_sum (256 threads)
 
 #pragma clang fp contract(off)
 
 namespace rcmvs {
 
 constexpr int MC_BLOCK = TM_BLOCK;
-constexpr int MC_TILE = RCMVS_MC_SCAN_TILE;
-constexpr int MC_PER = MC_TILE / MC_BLOCK;
-constexpr int MC_TOP = 1024;                                      // ceil(2^31 / 2048 / 2048) = 512 sums at the top level
 constexpr int MC_LIMIT = RCMVS_MC_SORT_LIMIT;
 constexpr int MC_HEAVY_GRID = 64;
-static_assert(2 * MC_TOP == RCMVS_MC_SCAN_WORK, "scan_work starts with MC_TOP uint64");
+static_assert(MC_BLOCK == SS_BLOCK, "zero_u64_kernel is launched with this family's block");
+static_assert(RCMVS_MC_SCAN_TILE == SS_TILE && RCMVS_MC_SCAN_WORK == SS_WORK, "mesh_clean.h describes scan_sort.h's work area");
 static_assert(MC_LIMIT * MC_BLOCK * 4 <= 64 * 1024, "the lanes' segments share one block's static LDS");
 
 using u64 = unsigned long long;
 
 __device__ inline long long mc_id() { return (long long)blockIdx.x * MC_BLOCK + threadIdx.x; }
-
-// ---- the three-level scan of one array (T: bytes or non-negative ints; every sum below 2^32) --------------------------------
-template <class T>
-__global__ __launch_bounds__(MC_BLOCK) void mc_tile_sum_kernel(const T* __restrict__ in, long long n, unsigned* __restrict__ tile) {
-    __shared__ unsigned sh[MC_BLOCK];
-    const long long base = (long long)blockIdx.x * MC_TILE + (long long)threadIdx.x * MC_PER;
-    unsigned s = 0;
-    for (int q = 0; q < MC_PER; ++q)
-        if (base + q < n) s += (unsigned)in[base + q];
-    const unsigned t = tm_block_sum(s, sh);
-    if (threadIdx.x == 0) tile[blockIdx.x] = t;
-}
-
-__global__ __launch_bounds__(MC_BLOCK) void mc_scan_up_kernel(const unsigned* __restrict__ tile, int nb1, u64* __restrict__ top) {
-    __shared__ u64 sh[MC_BLOCK];
-    const long long base = (long long)blockIdx.x * MC_TILE + (long long)threadIdx.x * MC_PER;
-    u64 a = 0;
-    for (int q = 0; q < MC_PER; ++q)
-        if (base + q < nb1) a += tile[base + q];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = MC_BLOCK / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) top[blockIdx.x] = sh[0];
-}
-
-__global__ void mc_scan_top_kernel(u64* __restrict__ top, int nb2, u64* __restrict__ total) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    u64 run = 0;
-    for (int b = 0; b < nb2; ++b) { const u64 c = top[b]; top[b] = run; run += c; }
-    *total = run;
-}
-
-__global__ __launch_bounds__(MC_BLOCK) void mc_scan_mid_kernel(unsigned* __restrict__ tile, int nb1, const u64* __restrict__ top) {
-    __shared__ unsigned sh[MC_BLOCK];
-    const long long base = (long long)blockIdx.x * MC_TILE + (long long)threadIdx.x * MC_PER;
-    unsigned c[MC_PER], s = 0;
-#pragma unroll
-    for (int q = 0; q < MC_PER; ++q) { c[q] = base + q < nb1 ? tile[base + q] : 0u; s += c[q]; }
-    unsigned run = tm_block_exclusive(s, sh) + (unsigned)top[blockIdx.x];
-#pragma unroll
-    for (int q = 0; q < MC_PER; ++q) { if (base + q < nb1) tile[base + q] = run; run += c[q]; }
-}
-
-template <class T>
-__global__ __launch_bounds__(MC_BLOCK) void mc_scan_down_kernel(const T* __restrict__ in, long long n, const unsigned* __restrict__ tile,
-                                                                const u64* __restrict__ total, int* __restrict__ out) {
-    __shared__ unsigned sh[MC_BLOCK];
-    const long long base = (long long)blockIdx.x * MC_TILE + (long long)threadIdx.x * MC_PER;
-    unsigned c[MC_PER], s = 0;
-#pragma unroll
-    for (int q = 0; q < MC_PER; ++q) { c[q] = base + q < n ? (unsigned)in[base + q] : 0u; s += c[q]; }
-    unsigned run = tm_block_exclusive(s, sh) + tile[blockIdx.x];
-#pragma unroll
-    for (int q = 0; q < MC_PER; ++q) { if (base + q < n) out[base + q] = (int)run; run += c[q]; }
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = (int)(unsigned)*total;
-}
-
-// out[0 .. n] = the exclusive prefix sums of in[0 .. n), *total = the sum; e0 / e1 as in RCMVS_LAUNCH_TIMED (either may be null)
-template <class T>
-static void mc_scan(const T* in, long long n, int* out, int* work, u64* total, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
-    const int nb1 = (int)(n > 0 ? cdiv(n, MC_TILE) : 1), nb2 = (int)cdiv(nb1, MC_TILE);
-    u64* top = reinterpret_cast<u64*>(work);
-    unsigned* tile = reinterpret_cast<unsigned*>(work) + 2 * MC_TOP;
-    hipEvent_t none = nullptr;
-    RCMVS_LAUNCH_TIMED(mc_tile_sum_kernel<T>, dim3(nb1), dim3(MC_BLOCK), 0, st, e0, none, in, n, tile);
-    hipLaunchKernelGGL(mc_scan_up_kernel, dim3(nb2), dim3(MC_BLOCK), 0, st, tile, nb1, top);
-    hipLaunchKernelGGL(mc_scan_top_kernel, dim3(1), dim3(64), 0, st, top, nb2, total);
-    hipLaunchKernelGGL(mc_scan_mid_kernel, dim3(nb2), dim3(MC_BLOCK), 0, st, tile, nb1, top);
-    RCMVS_LAUNCH_TIMED(mc_scan_down_kernel<T>, dim3(nb1), dim3(MC_BLOCK), 0, st, none, e1, in, n, tile, total, out);
-}
-
-__global__ __launch_bounds__(MC_BLOCK) void mc_zero_u64_kernel(u64* __restrict__ p, int n) {
-    if (blockIdx.x == 0 && (int)threadIdx.x < n) p[threadIdx.x] = 0;
-}
 
 // ---- components ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MC_BLOCK) void mc_init_kernel(int* __restrict__ label, int* __restrict__ comp_faces, int nv, u64* __restrict__ counts) {
@@ -437,12 +359,6 @@ static int mc_sizes(const char* what, int nv, int nf) {
     return 0;
 }
 
-static int mc_work(const char* what, const int* scan_work) {
-    RCMVS_REQUIRE(scan_work, "%s: null pointer", what);
-    RCMVS_REQUIRE((reinterpret_cast<uintptr_t>(scan_work) & 7) == 0, "%s: scan_work must be 8-byte aligned", what);
-    return 0;
-}
-
 }  // namespace rcmvs
 
 using namespace rcmvs;
@@ -469,12 +385,12 @@ extern "C" int rcmvs_mc_component_table_timed(const int* label, const int* comp_
     if (int rc = mc_sizes("mc_component_table", nv, 0)) return rc;
     RCMVS_REQUIRE(rank && totals && (nv == 0 || (label && comp_faces && flags)), "mc_component_table: null pointer");
     RCMVS_REQUIRE(capacity >= 0 && (table || capacity == 0), "mc_component_table: capacity = %d (>= 0, with a table)", capacity);
-    if (int rc = mc_work("mc_component_table", scan_work)) return rc;
+    if (int rc = scan_work_check("mc_component_table", scan_work)) return rc;
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(mc_zero_u64_kernel, dim3(1), dim3(MC_BLOCK), 0, st, e0, none, totals, 2);
+    RCMVS_LAUNCH_TIMED(zero_u64_kernel, dim3(1), dim3(MC_BLOCK), 0, st, e0, none, totals, 2);
     hipLaunchKernelGGL(mc_root_flag_kernel, dim3(mc_blocks(nv)), dim3(MC_BLOCK), 0, st, label, comp_faces, nv, flags, totals);
-    mc_scan<unsigned char>(flags, nv, rank, scan_work, totals, st, none, none);
+    scan3<unsigned char>(flags, nv, rank, scan_work, totals, st, none, none);
     RCMVS_LAUNCH_TIMED(mc_table_kernel, dim3(mc_blocks(nv)), dim3(MC_BLOCK), 0, st, none, e1, comp_faces, nv, flags, rank, table, capacity);
     return launch_status("mc_component_table");
 }
@@ -493,17 +409,17 @@ extern "C" int rcmvs_mc_select_timed(const int* faces, const unsigned char* face
                   "mc_select: null pointer");
     RCMVS_REQUIRE(min_faces >= 0 && keep_largest >= 0, "mc_select: min_faces = %d, keep_largest = %d (>= 0 each)", min_faces, keep_largest);
     RCMVS_REQUIRE(std::isfinite(min_fraction), "mc_select: min_fraction = %g (finite)", min_fraction);
-    if (int rc = mc_work("mc_select", scan_work)) return rc;
+    if (int rc = scan_work_check("mc_select", scan_work)) return rc;
     const mc::Select sel = {min_faces, min_fraction, max_faces, keep_largest, k_faces, k_label};
     const int drop = drop_unreferenced != 0;
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(mc_zero_u64_kernel, dim3(1), dim3(MC_BLOCK), 0, st, e0, none, totals, 3);
+    RCMVS_LAUNCH_TIMED(zero_u64_kernel, dim3(1), dim3(MC_BLOCK), 0, st, e0, none, totals, 3);
     hipLaunchKernelGGL(mc_vert_init_kernel, dim3(mc_blocks(nv)), dim3(MC_BLOCK), 0, st, label, comp_faces, nv, sel, drop, vert_keep, totals);
     hipLaunchKernelGGL(mc_face_keep_kernel, dim3(mc_blocks(nf)), dim3(MC_BLOCK), 0, st, faces, face_ok, label, comp_faces, nv, nf, sel, drop, face_keep,
                        vert_keep);
-    mc_scan<unsigned char>(face_keep, nf, face_rank, scan_work, totals, st, none, none);
-    mc_scan<unsigned char>(vert_keep, nv, vert_rank, scan_work, totals + 1, st, none, e1);
+    scan3<unsigned char>(face_keep, nf, face_rank, scan_work, totals, st, none, none);
+    scan3<unsigned char>(vert_keep, nv, vert_rank, scan_work, totals + 1, st, none, e1);
     return launch_status("mc_select");
 }
 
@@ -547,12 +463,12 @@ extern "C" int rcmvs_mc_adjacency_timed(const int* faces, int nv, int nf, int* r
                   "mc_adjacency: null pointer");
     RCMVS_REQUIRE(heavy_capacity >= 6ll * nf / (MC_LIMIT + 1) + 1, "mc_adjacency: heavy_capacity = %d (at least 6 nf / %d + 1)", heavy_capacity,
                   MC_LIMIT + 1);
-    if (int rc = mc_work("mc_adjacency", scan_work)) return rc;
+    if (int rc = scan_work_check("mc_adjacency", scan_work)) return rc;
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
     RCMVS_LAUNCH_TIMED(mc_zero_int_kernel, dim3(mc_blocks(nv)), dim3(MC_BLOCK), 0, st, e0, none, cursor, nv, stats);
     hipLaunchKernelGGL(mc_degree_kernel, dim3(mc_blocks(nf)), dim3(MC_BLOCK), 0, st, faces, nv, nf, cursor);
-    mc_scan<int>(cursor, nv, row_start, scan_work, stats + 5, st, none, none);
+    scan3<int>(cursor, nv, row_start, scan_work, stats + 5, st, none, none);
     hipLaunchKernelGGL(mc_fill_kernel, dim3(mc_blocks(nf)), dim3(MC_BLOCK), 0, st, faces, nv, nf, row_start, cursor, nbr);
     hipLaunchKernelGGL(mc_sort_kernel, dim3(mc_blocks(nv)), dim3(MC_BLOCK), 0, st, nv, row_start, row_len, nbr, mult, on_boundary, heavy, heavy_capacity,
                        stats);

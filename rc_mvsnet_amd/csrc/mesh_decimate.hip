@@ -2,7 +2,7 @@
 // simplification; rc_mvsnet_amd/mesh_decimate.py; contract in mesh_decimate.h, the per-element rules in mesh_decimate_math.h).
 //
 //   bounds     the box of the finite vertices as integer-ordered keys: block minima / maxima in LDS, then atomicMin / atomicMax.
-//   cluster    63-bit cell keys, an LSD radix sort of (key, vertex) pairs, 8 bits a pass (pc_register.hip's scheme: per-block
+//   cluster    63-bit cell keys, an LSD radix sort of (key, vertex) pairs, 8 bits a pass (scan_sort.hip's kernels: per-block
 //              digit histograms, one scan over the digit-major (digit, block) table, a stable scatter whose in-block rank comes
 //              from wave ballots), only as many passes as the lattice needs, ending in either buffer.  Segment heads + scan
 //              number the clusters; stable passes from vertex order leave every cluster's members ascending.
@@ -14,7 +14,7 @@
 //   place      one thread per cluster: the members' mean in ascending vertex order, the regularised quadric minimiser by Cramer's
 //              rule or the mean, integer colour sums.
 //   select     flags and ranks of the kept faces and the clusters they use, for mesh_clean's gather.
-//   scan       flags or counts -> exclusive prefix sums in three levels (mesh_clean.hip's scheme, this family's own copy).
+//   scan       flags or counts -> exclusive prefix sums in three levels: scan_sort.hip's scan3, which the radix passes use too.
 // No thread waits for another workgroup and there are no floating-point atomics.  gfx950 only; __syncthreads, ballots, plain
 // loads and stores and integer atomics (tests/emu compiles this file too).
 #include <cmath>
@@ -23,20 +23,17 @@
 #include "common.h"
 #include "mesh_decimate.h"
 #include "mesh_decimate_math.h"
-#include "tsdf_mesh_cells.h"                                      // tm_block_sum, tm_block_exclusive (256 threads)
+#include "scan_sort.h"                                            // scan3, radix_hist_kernel, radix_scatter_kernel, zero_u64_kernel
+#include "tsdf_mesh_cells.h"                                      // tm_block_sum (256 threads)
 
 #pragma clang fp contract(off)
 
 namespace rcmvs {
 
 constexpr int MD_BLOCK = TM_BLOCK;
-constexpr int MD_WAVES = MD_BLOCK / WAVE;
-constexpr int MD_TILE = RCMVS_MD_SCAN_TILE;
-constexpr int MD_PER = MD_TILE / MD_BLOCK;
-constexpr int MD_TOP = 1024;                                      // ceil(2^31 / 2048 / 2048) = 512 sums at the top level
 constexpr int MD_BOUNDS_GRID = 1024;
-static_assert(MD_BLOCK == RCMVS_MD_SORT_BLOCK, "a sort block is one workgroup's threads");
-static_assert(2 * MD_TOP == RCMVS_MD_SCAN_WORK, "scan_work starts with MD_TOP uint64");
+static_assert(MD_BLOCK == RCMVS_MD_SORT_BLOCK && MD_BLOCK == SS_BLOCK, "a sort block is one workgroup's threads");
+static_assert(RCMVS_MD_SCAN_TILE == SS_TILE && RCMVS_MD_SCAN_WORK == SS_WORK, "mesh_decimate.h describes scan_sort.h's work area");
 
 using u64 = unsigned long long;
 
@@ -48,133 +45,6 @@ struct MdLattice {
 
 __device__ inline long long md_id() { return (long long)blockIdx.x * MD_BLOCK + threadIdx.x; }
 
-// ---- the three-level scan of one array (T: bytes or non-negative ints; every sum below 2^32) --------------------------------
-template <class T>
-__global__ __launch_bounds__(MD_BLOCK) void md_tile_sum_kernel(const T* __restrict__ in, long long n, unsigned* __restrict__ tile) {
-    __shared__ unsigned sh[MD_BLOCK];
-    const long long base = (long long)blockIdx.x * MD_TILE + (long long)threadIdx.x * MD_PER;
-    unsigned s = 0;
-    for (int q = 0; q < MD_PER; ++q)
-        if (base + q < n) s += (unsigned)in[base + q];
-    const unsigned t = tm_block_sum(s, sh);
-    if (threadIdx.x == 0) tile[blockIdx.x] = t;
-}
-
-__global__ __launch_bounds__(MD_BLOCK) void md_scan_up_kernel(const unsigned* __restrict__ tile, int nb1, u64* __restrict__ top) {
-    __shared__ u64 sh[MD_BLOCK];
-    const long long base = (long long)blockIdx.x * MD_TILE + (long long)threadIdx.x * MD_PER;
-    u64 a = 0;
-    for (int q = 0; q < MD_PER; ++q)
-        if (base + q < nb1) a += tile[base + q];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = MD_BLOCK / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) top[blockIdx.x] = sh[0];
-}
-
-__global__ void md_scan_top_kernel(u64* __restrict__ top, int nb2, u64* __restrict__ total) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    u64 run = 0;
-    for (int b = 0; b < nb2; ++b) { const u64 c = top[b]; top[b] = run; run += c; }
-    *total = run;
-}
-
-__global__ __launch_bounds__(MD_BLOCK) void md_scan_mid_kernel(unsigned* __restrict__ tile, int nb1, const u64* __restrict__ top) {
-    __shared__ unsigned sh[MD_BLOCK];
-    const long long base = (long long)blockIdx.x * MD_TILE + (long long)threadIdx.x * MD_PER;
-    unsigned c[MD_PER], s = 0;
-#pragma unroll
-    for (int q = 0; q < MD_PER; ++q) { c[q] = base + q < nb1 ? tile[base + q] : 0u; s += c[q]; }
-    unsigned run = tm_block_exclusive(s, sh) + (unsigned)top[blockIdx.x];
-#pragma unroll
-    for (int q = 0; q < MD_PER; ++q) { if (base + q < nb1) tile[base + q] = run; run += c[q]; }
-}
-
-template <class T>
-__global__ __launch_bounds__(MD_BLOCK) void md_scan_down_kernel(const T* __restrict__ in, long long n, const unsigned* __restrict__ tile,
-                                                                const u64* __restrict__ total, int* __restrict__ out) {
-    __shared__ unsigned sh[MD_BLOCK];
-    const long long base = (long long)blockIdx.x * MD_TILE + (long long)threadIdx.x * MD_PER;
-    unsigned c[MD_PER], s = 0;
-#pragma unroll
-    for (int q = 0; q < MD_PER; ++q) { c[q] = base + q < n ? (unsigned)in[base + q] : 0u; s += c[q]; }
-    unsigned run = tm_block_exclusive(s, sh) + tile[blockIdx.x];
-#pragma unroll
-    for (int q = 0; q < MD_PER; ++q) { if (base + q < n) out[base + q] = (int)run; run += c[q]; }
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = (int)(unsigned)*total;
-}
-
-// out[0 .. n] = the exclusive prefix sums of in[0 .. n), *total = the sum (total null: kept in the work area's last top slot,
-// which no scan of at most 2^31 elements reaches); e0 / e1 as in RCMVS_LAUNCH_TIMED (either may be null)
-template <class T>
-static void md_scan(const T* in, long long n, int* out, int* work, u64* total, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
-    const int nb1 = (int)(n > 0 ? cdiv(n, MD_TILE) : 1), nb2 = (int)cdiv(nb1, MD_TILE);
-    u64* top = reinterpret_cast<u64*>(work);
-    unsigned* tile = reinterpret_cast<unsigned*>(work) + 2 * MD_TOP;
-    if (!total) total = top + (MD_TOP - 1);
-    hipEvent_t none = nullptr;
-    RCMVS_LAUNCH_TIMED(md_tile_sum_kernel<T>, dim3(nb1), dim3(MD_BLOCK), 0, st, e0, none, in, n, tile);
-    hipLaunchKernelGGL(md_scan_up_kernel, dim3(nb2), dim3(MD_BLOCK), 0, st, tile, nb1, top);
-    hipLaunchKernelGGL(md_scan_top_kernel, dim3(1), dim3(64), 0, st, top, nb2, total);
-    hipLaunchKernelGGL(md_scan_mid_kernel, dim3(nb2), dim3(MD_BLOCK), 0, st, tile, nb1, top);
-    RCMVS_LAUNCH_TIMED(md_scan_down_kernel<T>, dim3(nb1), dim3(MD_BLOCK), 0, st, none, e1, in, n, tile, total, out);
-}
-
-__global__ __launch_bounds__(MD_BLOCK) void md_zero_u64_kernel(u64* __restrict__ p, int n) {
-    if (blockIdx.x == 0 && (int)threadIdx.x < n) p[threadIdx.x] = 0;
-}
-
-// ---- the radix sort of (key, index) pairs (K: u64 or unsigned) ------------------------------------------------------------------
-// hist[d * nblk + b] = the keys of block b whose digit (bits shift .. shift + 7) is d
-template <class K>
-__global__ __launch_bounds__(MD_BLOCK) void md_radix_hist_kernel(const K* __restrict__ key, long long n, int shift, long long nblk,
-                                                                 int* __restrict__ hist) {
-    __shared__ int h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const long long i = md_id();
-    if (i < n) atomicAdd(&h[(int)((key[i] >> shift) & (K)255)], 1);
-    __syncthreads();
-    hist[(long long)threadIdx.x * nblk + blockIdx.x] = h[threadIdx.x];
-}
-
-// stable: a key goes to start[digit][block] + the keys of the same digit before it in the block (waves before it, lanes before it)
-template <class K>
-__global__ __launch_bounds__(MD_BLOCK) void md_radix_scatter_kernel(const K* __restrict__ key_in, const int* __restrict__ idx_in, long long n,
-                                                                    int shift, long long nblk, const int* __restrict__ start,
-                                                                    K* __restrict__ key_out, int* __restrict__ idx_out) {
-    __shared__ int wh[MD_WAVES][256];
-#pragma unroll
-    for (int w = 0; w < MD_WAVES; ++w) wh[w][threadIdx.x] = 0;
-    __syncthreads();
-    const long long i = md_id();
-    const bool valid = i < n;
-    const K k = valid ? key_in[i] : (K)0;
-    const int d = (int)((k >> shift) & (K)255);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const bool bit = (d >> b) & 1;
-        const unsigned long long m = __ballot(valid && bit);
-        peers &= bit ? m : ~m;
-    }
-    const int before = __popcll(peers & ((1ull << lane) - 1ull));
-    if (valid && before == 0) wh[wave][d] = __popcll(peers);
-    __syncthreads();
-    if (valid) {
-        long long dst = (long long)start[(long long)d * nblk + blockIdx.x] + before;
-        for (int w = 0; w < wave; ++w) dst += wh[w][d];
-        if (dst >= 0 && dst < n) {
-            key_out[dst] = k;
-            idx_out[dst] = idx_in[i];
-        }
-    }
-}
-
 // `passes` stable passes from (*ka, *ia); on return *ka / *ia point at the buffers that hold the sorted pairs
 template <class K>
 static void md_sort(K** ka, int** ia, K** kb, int** ib, long long n, int passes, int* hist, int* hist_start, int* scan_work, hipStream_t st) {
@@ -182,9 +52,9 @@ static void md_sort(K** ka, int** ia, K** kb, int** ib, long long n, int passes,
     const long long nblk = cdiv(n, MD_BLOCK);
     hipEvent_t none = nullptr;
     for (int p = 0; p < passes; ++p) {
-        hipLaunchKernelGGL(md_radix_hist_kernel<K>, dim3((unsigned)nblk), dim3(MD_BLOCK), 0, st, *ka, n, 8 * p, nblk, hist);
-        md_scan<int>(hist, 256 * nblk, hist_start, scan_work, nullptr, st, none, none);
-        hipLaunchKernelGGL(md_radix_scatter_kernel<K>, dim3((unsigned)nblk), dim3(MD_BLOCK), 0, st, *ka, *ia, n, 8 * p, nblk, hist_start, *kb, *ib);
+        hipLaunchKernelGGL(radix_hist_kernel<K>, dim3((unsigned)nblk), dim3(MD_BLOCK), 0, st, *ka, n, 8 * p, nblk, hist);
+        scan3<int>(hist, 256 * nblk, hist_start, scan_work, nullptr, st, none, none);
+        hipLaunchKernelGGL(radix_scatter_kernel<K>, dim3((unsigned)nblk), dim3(MD_BLOCK), 0, st, *ka, *ia, n, 8 * p, nblk, hist_start, *kb, *ib);
         K* tk = *ka; *ka = *kb; *kb = tk;
         int* ti = *ia; *ia = *ib; *ib = ti;
     }
@@ -543,12 +413,6 @@ static int md_sizes(const char* what, int nv, int nf) {
     return 0;
 }
 
-static int md_work(const char* what, const int* scan_work) {
-    RCMVS_REQUIRE(scan_work, "%s: null pointer", what);
-    RCMVS_REQUIRE((reinterpret_cast<uintptr_t>(scan_work) & 7) == 0, "%s: scan_work must be 8-byte aligned", what);
-    return 0;
-}
-
 static int md_lattice_args(const char* what, const double* lattice_host, const long long* dims_host, MdLattice* L) {
     RCMVS_REQUIRE(lattice_host && dims_host, "%s: null pointer", what);
     for (int a = 0; a < 3; ++a) { L->org[a] = lattice_host[a]; L->g[a] = dims_host[a]; }
@@ -606,15 +470,15 @@ extern "C" int rcmvs_md_cluster_timed(const float* verts, int nv, const double* 
     RCMVS_REQUIRE(head_rank && cluster_start && totals &&
                   (nv == 0 || (verts && key_a && idx_a && key_b && idx_b && hist && hist_start && head && cluster && order && cluster_key)),
                   "md_cluster: null pointer");
-    if (int rc = md_work("md_cluster", scan_work)) return rc;
+    if (int rc = scan_work_check("md_cluster", scan_work)) return rc;
     const u64 behind = (u64)L.g[0] * (u64)L.g[1] * (u64)L.g[2];   // <= 2^63: the key of the vertices that are not clustered
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(md_zero_u64_kernel, dim3(1), dim3(MD_BLOCK), 0, st, e0, none, totals, 2);
+    RCMVS_LAUNCH_TIMED(zero_u64_kernel, dim3(1), dim3(MD_BLOCK), 0, st, e0, none, totals, 2);
     hipLaunchKernelGGL(md_vertex_key_kernel, dim3(md_blocks(nv)), dim3(MD_BLOCK), 0, st, verts, nv, L, behind, key_a, idx_a, totals);
     md_sort<u64>(&key_a, &idx_a, &key_b, &idx_b, nv, md_passes(behind), hist, hist_start, scan_work, st);
     hipLaunchKernelGGL(md_head_kernel, dim3(md_blocks(nv)), dim3(MD_BLOCK), 0, st, key_a, nv, behind, head);
-    md_scan<unsigned char>(head, nv, head_rank, scan_work, totals, st, none, none);
+    scan3<unsigned char>(head, nv, head_rank, scan_work, totals, st, none, none);
     RCMVS_LAUNCH_TIMED(md_emit_kernel, dim3(md_blocks(nv)), dim3(MD_BLOCK), 0, st, none, e1, key_a, idx_a, head, head_rank, nv, behind, totals, cluster, order,
                        cluster_start, cluster_key);
     return launch_status("md_cluster");
@@ -657,7 +521,7 @@ extern "C" int rcmvs_md_quadrics_timed(const float* verts, const int* faces, int
     if (int rc = md_lattice_args("md_quadrics", lattice_host, dims_host, &L)) return rc;
     RCMVS_REQUIRE(verts && cluster && cluster_key && seg && quad && (nf == 0 || (faces && ckey_a && cidx_a && ckey_b && cidx_b && hist && hist_start)),
                   "md_quadrics: null pointer");
-    if (int rc = md_work("md_quadrics", scan_work)) return rc;
+    if (int rc = scan_work_check("md_quadrics", scan_work)) return rc;
     const long long n = 3ll * nf;
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
@@ -690,7 +554,7 @@ extern "C" int rcmvs_md_place_timed(const float* verts, const unsigned char* rgb
     RCMVS_REQUIRE(!out_rgb || rgb, "md_place: null pointer (out_rgb needs rgb)");
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(md_zero_u64_kernel, dim3(1), dim3(MD_BLOCK), 0, st, e0, none, counts, 3);
+    RCMVS_LAUNCH_TIMED(zero_u64_kernel, dim3(1), dim3(MD_BLOCK), 0, st, e0, none, counts, 3);
     RCMVS_LAUNCH_TIMED(md_place_kernel, dim3(md_blocks(m)), dim3(MD_BLOCK), 0, st, none, e1, verts, rgb, nv, order, cluster_start, cluster_key, m, L, quad,
                        placement, reg, out_verts, out_rgb, via, counts);
     return launch_status("md_place");
@@ -708,14 +572,14 @@ extern "C" int rcmvs_md_select_timed(const int* cface, const unsigned char* face
                                      void* stream) {
     if (int rc = md_sizes("md_select", m, nf)) return rc;
     RCMVS_REQUIRE(face_rank && vert_rank && totals && (nf == 0 || (cface && face_class && face_keep)) && (m == 0 || vert_keep), "md_select: null pointer");
-    if (int rc = md_work("md_select", scan_work)) return rc;
+    if (int rc = scan_work_check("md_select", scan_work)) return rc;
     const int drop = drop_unreferenced != 0;
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
     RCMVS_LAUNCH_TIMED(md_vert_init_kernel, dim3(md_blocks(m)), dim3(MD_BLOCK), 0, st, e0, none, vert_keep, m, drop);
     hipLaunchKernelGGL(md_face_keep_kernel, dim3(md_blocks(nf)), dim3(MD_BLOCK), 0, st, cface, face_class, m, nf, drop, face_keep, vert_keep);
-    md_scan<unsigned char>(face_keep, nf, face_rank, scan_work, totals, st, none, none);
-    md_scan<unsigned char>(vert_keep, m, vert_rank, scan_work, totals + 1, st, none, e1);
+    scan3<unsigned char>(face_keep, nf, face_rank, scan_work, totals, st, none, none);
+    scan3<unsigned char>(vert_keep, m, vert_rank, scan_work, totals + 1, st, none, e1);
     return launch_status("md_select");
 }
 

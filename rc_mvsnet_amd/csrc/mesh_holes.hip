@@ -8,7 +8,7 @@
 //   leaders    one thread per vertex; a simple vertex smaller than its successor and its predecessor walks the finished succ
 //              array until it meets a smaller vertex, a -1, itself, or has made max_edges steps.  Nothing is written that the
 //              launch reads.  Then block sums of the loop statistics, one integer atomic each per block.
-//   scan       counts -> exclusive prefix sums in three levels (mesh_clean.hip's scheme, this family's own copy).
+//   scan       counts -> exclusive prefix sums in three levels: scan_sort.hip's scan3.
 //   emit       bit copies of the input, then one lane per leader walks its loop once more: fp64 sum in loop order, integer colour
 //              sums, the faces at the ranks the scans gave.
 // No kernel reads a cell that another workgroup of the same launch writes, none waits for another workgroup, and there are no
@@ -19,95 +19,21 @@
 #include "common.h"
 #include "mesh_holes.h"
 #include "mesh_holes_math.h"
-#include "tsdf_mesh_cells.h"                                      // tm_block_sum, tm_block_exclusive (256 threads)
+#include "scan_sort.h"                                            // scan3, zero_u64_kernel
+#include "tsdf_mesh_cells.h"                                      // tm_block_sum (256 threads)
 
 #pragma clang fp contract(off)
 
 namespace rcmvs {
 
 constexpr int MH_BLOCK = TM_BLOCK;
-constexpr int MH_TILE = RCMVS_MH_SCAN_TILE;
-constexpr int MH_PER = MH_TILE / MH_BLOCK;
-constexpr int MH_TOP = 1024;                                      // ceil(2^31 / 2048 / 2048) = 512 sums at the top level
-static_assert(2 * MH_TOP == RCMVS_MH_SCAN_WORK, "scan_work starts with MH_TOP uint64");
+static_assert(MH_BLOCK == SS_BLOCK, "zero_u64_kernel is launched with this family's block");
+static_assert(RCMVS_MH_SCAN_TILE == SS_TILE && RCMVS_MH_SCAN_WORK == SS_WORK, "mesh_holes.h describes scan_sort.h's work area");
 static_assert(mh::NONE == RCMVS_MH_NONE && mh::SIMPLE == RCMVS_MH_SIMPLE && mh::COMPLEX == RCMVS_MH_COMPLEX, "the flags of mesh_holes.h");
 
 using u64 = unsigned long long;
 
 __device__ inline long long mh_id() { return (long long)blockIdx.x * MH_BLOCK + threadIdx.x; }
-
-// ---- the three-level scan of one array (T: bytes or non-negative ints; every sum below 2^32) --------------------------------
-template <class T>
-__global__ __launch_bounds__(MH_BLOCK) void mh_tile_sum_kernel(const T* __restrict__ in, long long n, unsigned* __restrict__ tile) {
-    __shared__ unsigned sh[MH_BLOCK];
-    const long long base = (long long)blockIdx.x * MH_TILE + (long long)threadIdx.x * MH_PER;
-    unsigned s = 0;
-    for (int q = 0; q < MH_PER; ++q)
-        if (base + q < n) s += (unsigned)in[base + q];
-    const unsigned t = tm_block_sum(s, sh);
-    if (threadIdx.x == 0) tile[blockIdx.x] = t;
-}
-
-__global__ __launch_bounds__(MH_BLOCK) void mh_scan_up_kernel(const unsigned* __restrict__ tile, int nb1, u64* __restrict__ top) {
-    __shared__ u64 sh[MH_BLOCK];
-    const long long base = (long long)blockIdx.x * MH_TILE + (long long)threadIdx.x * MH_PER;
-    u64 a = 0;
-    for (int q = 0; q < MH_PER; ++q)
-        if (base + q < nb1) a += tile[base + q];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = MH_BLOCK / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) top[blockIdx.x] = sh[0];
-}
-
-__global__ void mh_scan_top_kernel(u64* __restrict__ top, int nb2, u64* __restrict__ total) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    u64 run = 0;
-    for (int b = 0; b < nb2; ++b) { const u64 c = top[b]; top[b] = run; run += c; }
-    *total = run;
-}
-
-__global__ __launch_bounds__(MH_BLOCK) void mh_scan_mid_kernel(unsigned* __restrict__ tile, int nb1, const u64* __restrict__ top) {
-    __shared__ unsigned sh[MH_BLOCK];
-    const long long base = (long long)blockIdx.x * MH_TILE + (long long)threadIdx.x * MH_PER;
-    unsigned c[MH_PER], s = 0;
-#pragma unroll
-    for (int q = 0; q < MH_PER; ++q) { c[q] = base + q < nb1 ? tile[base + q] : 0u; s += c[q]; }
-    unsigned run = tm_block_exclusive(s, sh) + (unsigned)top[blockIdx.x];
-#pragma unroll
-    for (int q = 0; q < MH_PER; ++q) { if (base + q < nb1) tile[base + q] = run; run += c[q]; }
-}
-
-template <class T>
-__global__ __launch_bounds__(MH_BLOCK) void mh_scan_down_kernel(const T* __restrict__ in, long long n, const unsigned* __restrict__ tile,
-                                                                const u64* __restrict__ total, int* __restrict__ out) {
-    __shared__ unsigned sh[MH_BLOCK];
-    const long long base = (long long)blockIdx.x * MH_TILE + (long long)threadIdx.x * MH_PER;
-    unsigned c[MH_PER], s = 0;
-#pragma unroll
-    for (int q = 0; q < MH_PER; ++q) { c[q] = base + q < n ? (unsigned)in[base + q] : 0u; s += c[q]; }
-    unsigned run = tm_block_exclusive(s, sh) + tile[blockIdx.x];
-#pragma unroll
-    for (int q = 0; q < MH_PER; ++q) { if (base + q < n) out[base + q] = (int)run; run += c[q]; }
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = (int)(unsigned)*total;
-}
-
-// out[0 .. n] = the exclusive prefix sums of in[0 .. n), *total = the sum; e1 as in RCMVS_LAUNCH_TIMED (may be null)
-template <class T>
-static void mh_scan(const T* in, long long n, int* out, int* work, u64* total, hipStream_t st, hipEvent_t e1) {
-    const int nb1 = (int)(n > 0 ? cdiv(n, MH_TILE) : 1), nb2 = (int)cdiv(nb1, MH_TILE);
-    u64* top = reinterpret_cast<u64*>(work);
-    unsigned* tile = reinterpret_cast<unsigned*>(work) + 2 * MH_TOP;
-    hipEvent_t none = nullptr;
-    hipLaunchKernelGGL(mh_tile_sum_kernel<T>, dim3(nb1), dim3(MH_BLOCK), 0, st, in, n, tile);
-    hipLaunchKernelGGL(mh_scan_up_kernel, dim3(nb2), dim3(MH_BLOCK), 0, st, tile, nb1, top);
-    hipLaunchKernelGGL(mh_scan_top_kernel, dim3(1), dim3(64), 0, st, top, nb2, total);
-    hipLaunchKernelGGL(mh_scan_mid_kernel, dim3(nb2), dim3(MH_BLOCK), 0, st, tile, nb1, top);
-    RCMVS_LAUNCH_TIMED(mh_scan_down_kernel<T>, dim3(nb1), dim3(MH_BLOCK), 0, st, none, e1, in, n, tile, total, out);
-}
 
 // ---- boundary -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MH_BLOCK) void mh_init_kernel(int nv, int* __restrict__ out_count, int* __restrict__ in_count, int* __restrict__ succ,
@@ -171,10 +97,6 @@ __global__ __launch_bounds__(MH_BLOCK) void mh_classify_kernel(int nv, const int
 }
 
 // ---- leaders ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(MH_BLOCK) void mh_zero_u64_kernel(u64* __restrict__ p, int n) {
-    if (blockIdx.x == 0 && (int)threadIdx.x < n) p[threadIdx.x] = 0;
-}
-
 // The length of the loop that v leads, 0 when v leads none of at most max_edges edges.  succ and pred are only read.  A vertex
 // that is not simple has succ == pred == -1 and fails the first test; the walk leaves a loop's vertices only through a -1.
 __device__ inline int mh_loop_length(const int* __restrict__ succ, const int* __restrict__ pred, int nv, int v, int max_edges) {
@@ -314,13 +236,13 @@ extern "C" int rcmvs_mh_leaders_timed(const int* succ, const int* pred, int nv, 
     RCMVS_REQUIRE(max_edges >= 3 && max_edges <= RCMVS_MH_MAX_EDGES, "mh_leaders: max_edges = %d (3 .. %d)", max_edges, RCMVS_MH_MAX_EDGES);
     RCMVS_REQUIRE(vert_rank && face_rank && totals && scan_work && (nv == 0 || (succ && pred && loop_len && vert_count && face_count)),
                   "mh_leaders: null pointer");
-    RCMVS_REQUIRE((reinterpret_cast<uintptr_t>(scan_work) & 7) == 0, "mh_leaders: scan_work must be 8-byte aligned");
+    if (int rc = scan_work_check("mh_leaders", scan_work)) return rc;
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(mh_zero_u64_kernel, dim3(1), dim3(MH_BLOCK), 0, st, e0, none, totals, 5);
+    RCMVS_LAUNCH_TIMED(zero_u64_kernel, dim3(1), dim3(MH_BLOCK), 0, st, e0, none, totals, 5);
     hipLaunchKernelGGL(mh_leader_kernel, dim3(mh_blocks(nv)), dim3(MH_BLOCK), 0, st, succ, pred, nv, max_edges, loop_len, vert_count, face_count, totals);
-    mh_scan<unsigned char>(vert_count, nv, vert_rank, scan_work, totals, st, none);
-    mh_scan<int>(face_count, nv, face_rank, scan_work, totals + 1, st, e1);
+    scan3<unsigned char>(vert_count, nv, vert_rank, scan_work, totals, st, none, none);
+    scan3<int>(face_count, nv, face_rank, scan_work, totals + 1, st, none, e1);
     return launch_status("mh_leaders");
 }
 

@@ -5,8 +5,9 @@
 //   crop      one thread per point: optional 4x4 transform in fp64 (rounded to fp32 once), axis range + even-odd polygon test
 //             (pc_register_math.h), per-block counts, pointcloud.hip's scan, ordered compaction of the transformed points.
 //   voxel     63-bit voxel keys (kz, ky, kx packed on the lattice's own dims), an LSD radix sort of (key, index) pairs, 8 bits a
-//             pass: per-block digit histograms, one scan over the digit-major (digit, block) table, a stable scatter whose
-//             in-block rank comes from wave ballots.  Stable passes from index order leave every voxel's points in input order.
+//             pass (scan_sort.hip's kernels, shared with mesh_decimate.hip): per-block digit histograms, one scan over the
+//             digit-major (digit, block) table, a stable scatter whose in-block rank comes from wave ballots.  Stable
+//             passes from index order leave every voxel's points in input order.
 //             Segment heads + scan give the voxel count and the output slots; one thread per head then walks its segment and
 //             adds in fp64 in that order (a long segment occupies one lane, never a block).  No array over the lattice, no
 //             floating-point atomics.
@@ -20,6 +21,7 @@
 #include "common.h"
 #include "pc_register.h"
 #include "pc_register_math.h"
+#include "scan_sort.h"                                            // radix_hist_kernel, radix_scatter_kernel
 
 #pragma clang fp contract(off)
 
@@ -42,6 +44,7 @@ constexpr int PCR_WAVES = PCR_BLOCK / WAVE;
 constexpr int PCR_ICP_BLOCKS = RCMVS_PC_ICP_BLOCKS;
 constexpr int PCR_NMOM = RCMVS_PC_ICP_MOMENTS;
 constexpr int PCR_HIST_BLOCKS = 1024;
+static_assert(PCR_BLOCK == SS_BLOCK, "the radix kernels of scan_sort.h sort blocks of PCR_BLOCK keys");
 
 // ---- transform + crop -----------------------------------------------------------------------------------------------
 struct PcrCrop {
@@ -103,49 +106,6 @@ __global__ __launch_bounds__(PCR_BLOCK) void pcr_voxel_key_kernel(const float* _
     const long long kz = pcr::voxel_coord(pts[(long long)i * 3 + 2], L.org[2], L.voxel);
     key[i] = (unsigned long long)((kz * L.g[1] + ky) * L.g[0] + kx);
     idx[i] = i;
-}
-
-// hist[d * nblk + b] = the keys of block b whose digit (bits shift .. shift + 7) is d
-__global__ __launch_bounds__(PCR_BLOCK) void pcr_radix_hist_kernel(const unsigned long long* __restrict__ key, int n, int shift, int nblk,
-                                                                   int* __restrict__ hist) {
-    __shared__ int h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const int i = blockIdx.x * PCR_BLOCK + threadIdx.x;
-    if (i < n) atomicAdd(&h[(int)((key[i] >> shift) & 255ull)], 1);
-    __syncthreads();
-    hist[(long long)threadIdx.x * nblk + blockIdx.x] = h[threadIdx.x];
-}
-
-// stable: a key goes to start[digit][block] + the keys of the same digit before it in the block (waves before it, lanes before it)
-__global__ __launch_bounds__(PCR_BLOCK) void pcr_radix_scatter_kernel(const unsigned long long* __restrict__ key_in, const int* __restrict__ idx_in,
-                                                                      int n, int shift, int nblk, const int* __restrict__ start,
-                                                                      unsigned long long* __restrict__ key_out, int* __restrict__ idx_out) {
-    __shared__ int wh[PCR_WAVES][256];
-#pragma unroll
-    for (int w = 0; w < PCR_WAVES; ++w) wh[w][threadIdx.x] = 0;
-    __syncthreads();
-    const int i = blockIdx.x * PCR_BLOCK + threadIdx.x;
-    const bool valid = i < n;
-    const unsigned long long k = valid ? key_in[i] : 0ull;
-    const int d = (int)((k >> shift) & 255ull);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const bool bit = (d >> b) & 1;
-        const unsigned long long m = __ballot(valid && bit);
-        peers &= bit ? m : ~m;
-    }
-    const int before = __popcll(peers & ((1ull << lane) - 1ull));
-    if (valid && before == 0) wh[wave][d] = __popcll(peers);
-    __syncthreads();
-    if (valid) {
-        int dst = start[(long long)d * nblk + blockIdx.x] + before;
-        for (int w = 0; w < wave; ++w) dst += wh[w][d];
-        key_out[dst] = k;
-        idx_out[dst] = idx_in[i];
-    }
 }
 
 __global__ __launch_bounds__(PCR_BLOCK) void pcr_voxel_head_kernel(const unsigned long long* __restrict__ key, int n, int* __restrict__ head) {
@@ -387,9 +347,9 @@ extern "C" int rcmvs_pc_voxel_sort(const float* pts, long long n, const double* 
         const int* iin = p & 1 ? idx_b : idx_a;
         unsigned long long* kout = p & 1 ? key_a : key_b;
         int* iout = p & 1 ? idx_a : idx_b;
-        hipLaunchKernelGGL(pcr_radix_hist_kernel, dim3(nblk), dim3(PCR_BLOCK), 0, st, kin, (int)n, 8 * p, nblk, hist);
+        hipLaunchKernelGGL(radix_hist_kernel<unsigned long long>, dim3(nblk), dim3(PCR_BLOCK), 0, st, kin, n, 8 * p, (long long)nblk, hist);
         pcr_scan(hist, 256 * nblk, scan_work, hist_start, st);
-        hipLaunchKernelGGL(pcr_radix_scatter_kernel, dim3(nblk), dim3(PCR_BLOCK), 0, st, kin, iin, (int)n, 8 * p, nblk, hist_start, kout, iout);
+        hipLaunchKernelGGL(radix_scatter_kernel<unsigned long long>, dim3(nblk), dim3(PCR_BLOCK), 0, st, kin, iin, n, 8 * p, (long long)nblk, hist_start, kout, iout);
     }
     hipLaunchKernelGGL(pcr_voxel_head_kernel, dim3(nblk), dim3(PCR_BLOCK), 0, st, key_a, (int)n, head);
     pcr_scan(head, (int)n, scan_work, head_start, st);

@@ -37,6 +37,7 @@ def _ptr(t, name, dtype):
 
 
 def _scan_work(n, dev):
+    """the work area of csrc/scan_sort.hip's scan of up to n elements (the three mesh families' scan_work arguments)"""
     return torch.empty(SCAN_WORK + (n + SCAN_TILE - 1) // SCAN_TILE + 1, device=dev, dtype=torch.int32)
 
 

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, fusion, mesh_clean
-from .mesh_clean import _count, _mesh, _ptr, _real
+from .mesh_clean import _count, _mesh, _ptr, _real, _scan_work
 
 SCAN_TILE, SCAN_WORK, SORT_BLOCK, MAX_ELEMENTS, MAX_CELLS_PER_AXIS = (_lib.CONSTANTS["RCMVS_MD_" + k] for k in (
     "SCAN_TILE", "SCAN_WORK", "SORT_BLOCK", "MAX_ELEMENTS", "MAX_CELLS_PER_AXIS"))
@@ -39,10 +39,6 @@ DEFAULT_REG = 1e-3                                               # md::DEFAULT_R
 
 def _cdiv(a, b):
     return (a + b - 1) // b
-
-
-def _scan_work(n, dev):
-    return torch.empty(SCAN_WORK + _cdiv(n, SCAN_TILE) + 1, device=dev, dtype=torch.int32)
 
 
 def _sort_buffers(n, dev):

@@ -16,7 +16,7 @@ orientation) is skipped and counted; a lone triangle becomes two-sided; at most 
 import torch
 
 from . import _lib, fusion, mesh_clean
-from .mesh_clean import _count, _faces, _mesh, _ptr
+from .mesh_clean import _count, _faces, _mesh, _ptr, _scan_work
 
 MAX_EDGES, SCAN_TILE, SCAN_WORK = (_lib.CONSTANTS["RCMVS_MH_" + k] for k in ("MAX_EDGES", "SCAN_TILE", "SCAN_WORK"))
 NONE, SIMPLE, COMPLEX = (_lib.CONSTANTS["RCMVS_MH_" + k] for k in ("NONE", "SIMPLE", "COMPLEX"))
@@ -75,7 +75,7 @@ def leaders(bnd, max_edges):
     vert_rank = torch.empty(nv + 1, device=dev, dtype=torch.int32)
     face_rank = torch.empty(nv + 1, device=dev, dtype=torch.int32)
     totals = torch.empty(5, device=dev, dtype=torch.int64)
-    work = torch.empty(SCAN_WORK + (nv + SCAN_TILE - 1) // SCAN_TILE + 1, device=dev, dtype=torch.int32)
+    work = _scan_work(nv, dev)
     _lib.call("rcmvs_mh_leaders", _ptr(succ, "succ", torch.int32), _ptr(bnd["pred"], "pred", torch.int32), nv, max_edges,
               _ptr(loop_len, "loop_len", torch.int32), _ptr(vert_count, "vert_count", torch.uint8), _ptr(face_count, "face_count", torch.int32),
               fusion._chk(vert_rank, "vert_rank", torch.int32), fusion._chk(face_rank, "face_rank", torch.int32),

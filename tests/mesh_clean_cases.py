@@ -9,7 +9,7 @@ import torch
 
 import mesh_clean_oracle as O
 import tsdf_cases as C
-from rc_mvsnet_amd import dtu_io, mesh_clean as MC, tsdf_mesh as TM
+from rc_mvsnet_amd import _lib, dtu_io, fusion, mesh_clean as MC, tsdf_mesh as TM
 
 TILE, LIMIT = MC.SCAN_TILE, MC.SORT_LIMIT
 INT_MAX, INT_MIN = 2 ** 31 - 1, -2 ** 31
@@ -231,6 +231,32 @@ def check_parts(dev, name):
         assert heavy == 0 and int(want["row_start"][1]) == LIMIT
     if name == "fan_past_limit":
         assert heavy == 1 and int(want["row_start"][1]) == LIMIT + 2                   # a segment's length is even: two entries per face
+
+
+def check_scan_third_level(dev):
+    """rcmvs_mc_component_table on TILE * TILE + TILE + 1 vertices that are all roots: the smallest scan whose upper two levels run
+    two workgroups, the second partly filled, over two top sums.  Flags, ranks and totals against torch.cumsum in int64."""
+    nv = TILE * TILE + TILE + 1
+    v = torch.arange(nv, device=dev, dtype=torch.int32)
+    label, comp_faces = v, torch.where(v % 3 == 0, 1 + v % 5, torch.zeros_like(v))
+    want_flags = comp_faces > 0
+    want_rank = torch.cumsum(want_flags.to(torch.int64), 0) - want_flags.to(torch.int64)
+    count = int(want_flags.sum())
+
+    def run():
+        flags, rank = torch.empty(nv, device=dev, dtype=torch.uint8), torch.empty(nv + 1, device=dev, dtype=torch.int32)
+        totals, work = torch.empty(2, device=dev, dtype=torch.int64), MC._scan_work(nv, dev)
+        _lib.call("rcmvs_mc_component_table", MC._ptr(label, "label", torch.int32), MC._ptr(comp_faces, "comp_faces", torch.int32), nv,
+                  MC._ptr(flags, "flags", torch.uint8), MC._ptr(rank, "rank", torch.int32), MC._ptr(work, "scan_work", torch.int32),
+                  MC._ptr(None, "table", torch.int32), 0, MC._ptr(totals, "totals", torch.int64), fusion._stream())
+        return flags, rank, totals
+
+    flags, rank, totals = run()
+    print(f"third level: nv = {nv}, flagged = {count}, totals = {totals.tolist()}, rank[nv] = {int(rank[nv])}")
+    assert count == (nv + 2) // 3 and torch.equal(flags, want_flags.to(torch.uint8))
+    assert torch.equal(rank[:nv].to(torch.int64), want_rank)
+    assert int(rank[nv]) == count and totals.tolist() == [count, 5]
+    assert all(torch.equal(a, b) for a, b in zip(run(), (flags, rank, totals)))
 
 
 def check_clean(dev, name, k, twice=False):

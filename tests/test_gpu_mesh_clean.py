@@ -25,6 +25,10 @@ def test_clean_mesh_equals_the_oracle_and_two_runs_are_identical(name, k):
     MCC.check_clean(DEV, name, k, twice=True)
 
 
+def test_scan_reaches_its_third_level():
+    MCC.check_scan_third_level(DEV)
+
+
 def test_taubin_identities_and_pinning():
     MCC.check_smoothing_parts(DEV)
 

@@ -88,7 +88,7 @@ def main():
     assert torch.equal(succ, bnd["succ"]) and torch.equal(pred, bnd["pred"]) and torch.equal(flags, bnd["flags"])
     led = MH.leaders(bnd, args.max_edges)
     ll, vc, fc, vr, fr, tot = E(nv, torch.int32), E(nv, torch.uint8), E(nv, torch.int32), E(nv + 1, torch.int32), E(nv + 1, torch.int32), E(5, torch.int64)
-    lwork = E(MH.SCAN_WORK + (nv + MH.SCAN_TILE - 1) // MH.SCAN_TILE + 1, torch.int32)
+    lwork = MC._scan_work(nv, dev)
     l_ms = timed([lambda ev: _lib.call("rcmvs_mh_leaders_timed", i32(succ), i32(pred), nv, args.max_edges, i32(ll), u8(vc), i32(fc), i32(vr), i32(fr),
                                        i32(lwork), i64(tot), *ev_args(ev))], args.reps)
     assert torch.equal(ll, led["loop_len"]) and torch.equal(vr, led["vert_rank"]) and torch.equal(fr, led["face_rank"])
