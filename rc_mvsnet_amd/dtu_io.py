@@ -193,9 +193,17 @@ def read_ply_mesh_rgb(path):
 _COLOUR_PROPS = (("red", "green", "blue"), ("r", "g", "b"), ("diffuse_red", "diffuse_green", "diffuse_blue"))
 
 
-def _read_ply_mesh(path, colours):
-    """the reader behind read_ply_mesh and read_ply_mesh_rgb -> (verts, faces, rgb or None); colours False: rgb is not looked for"""
-    rgb = None
+def read_ply_mesh_normals(path):
+    """read_ply_mesh_rgb plus the vertex normals, in the same single pass -> (verts, faces, rgb (n,3) uint8 or None, normals (n,3)
+    float32 or None).  The normals are the vertex element's nx ny nz when all three are there as floating-point properties, with
+    their bits as stored when they are float; anything else gives None."""
+    return _read_ply_mesh(path, True, True)
+
+
+def _read_ply_mesh(path, colours, normals=False):
+    """the reader behind read_ply_mesh, read_ply_mesh_rgb and read_ply_mesh_normals -> (verts, faces, rgb or None), with normals
+    (verts, faces, rgb or None, normals or None); colours False: rgb is not looked for"""
+    rgb, nrm = None, None
     with open(path, "rb") as f:
         fmt, elements = _ply_header(f)
         names = [e[0] for e in elements]
@@ -210,6 +218,7 @@ def _read_ply_mesh(path, colours):
         if any(isinstance(t, tuple) for _, t in vprops):
             raise FormatError(f"{path}: list properties in the vertex element are not supported")
         triple = next((t for t in _COLOUR_PROPS if all(k in pnames and np.dtype(vprops[pnames.index(k)][1]) == np.uint8 for k in t)), None) if colours else None
+        ntriple = ("nx", "ny", "nz") if normals and all(k in pnames and np.dtype(vprops[pnames.index(k)][1]).kind == "f" for k in ("nx", "ny", "nz")) else None
         idx = None
         if face_name is not None:
             fprops = elements[names.index(face_name)][2]
@@ -231,6 +240,9 @@ def _read_ply_mesh(path, colours):
                     if triple is not None:
                         cols = [pnames.index(k) for k in triple]
                         rgb = np.array([[int(r[c]) for c in cols] for r in rows], dtype=np.uint8).reshape(count, 3)
+                    if ntriple is not None:
+                        cols = [pnames.index(k) for k in ntriple]
+                        nrm = np.array([[float(r[c]) for c in cols] for r in rows], dtype=np.float64).astype(np.float32).reshape(count, 3)
                 elif name == face_name:
                     bad = next((r for r, row in enumerate(rows) if len(row[idx]) != 3), None)
                     if bad is not None:
@@ -249,6 +261,8 @@ def _read_ply_mesh(path, colours):
                     verts = np.stack([rec[k].astype(np.float32) for k in ("x", "y", "z")], axis=1).reshape(count, 3)
                     if triple is not None:
                         rgb = np.stack([rec[k] for k in triple], axis=1).astype(np.uint8).reshape(count, 3)
+                    if ntriple is not None:
+                        nrm = np.stack([rec[k].astype(np.float32) for k in ntriple], axis=1).reshape(count, 3)
                     done += 1
                 elif name == face_name:
                     faces = _binary_faces(f, count, props, idx, end, path)
@@ -262,6 +276,8 @@ def _read_ply_mesh(path, colours):
     n = len(verts)
     if len(faces) and (faces.min() < 0 or faces.max() >= n):
         raise FormatError(f"{path}: face indices outside 0 .. {n - 1}")
+    if normals:
+        return verts, faces.astype(np.int32).reshape(-1, 3), rgb, nrm
     return verts, faces.astype(np.int32).reshape(-1, 3), rgb
 
 

@@ -12,8 +12,8 @@ visibility by a 64-bit integer minimum of (depth bits, face number): every outpu
         --depth-folder out/scan9
 
 Limits: no near-plane clipping (a face with a vertex nearer than ``near`` or more than 2^16 pixels from the image origin is dropped
-and counted as clipped); one sample per pixel, no anti-aliasing; flat shading with a light at the camera; vertex colours only, no
-texture; H, W <= 16384; pinhole cameras only.  No CPU fallback."""
+and counted as clipped); one sample per pixel, no anti-aliasing; the shade is flat, with a light at the camera; vertex colours only, no
+texture; smooth shading only with ``normals`` (``--normals``); H, W <= 16384; pinhole cameras only.  No CPU fallback."""
 import argparse
 import ctypes
 import json
@@ -62,14 +62,16 @@ def _arguments(verts, faces, rgb, cams, H, W, near, cull, background, what):
     return nv, nf, H, W, cams, near, CULL[cull], bg[0] | bg[1] << 8 | bg[2] << 16
 
 
-def render(verts, faces, rgb, cams, H, W, near=DEFAULT_NEAR, cull="none", background=(0, 0, 0), trace=None, _timed=None):
+def render(verts, faces, rgb, cams, H, W, near=DEFAULT_NEAR, cull="none", background=(0, 0, 0), trace=None, _timed=None, normals=None):
     """verts (nv,3) fp32, faces (nf,3) int32, rgb (nv,3) uint8 or None on the device; cams (V,16) float64 on the host, the rows of
     tsdf_mesh.camera_row; cull 'none' or 'back' (back: only faces whose normal (b - a) x (c - a) points at the camera, which is how
     the extracted meshes are oriented) -> dict of device tensors: depth (V,H,W) fp32 (0 where no face is seen), face (V,H,W) int32
     (-1 there), rgb (V,H,W,3) uint8 (white faces without vertex colours, ``background`` where no face is seen), shade (V,H,W) uint8,
     keys (V,H,W) int64 (depth bits << 32 | face number, -1 where no face is seen) and stats (V, STATS) int64, the counters of
     STAT_NAMES per view (``stats_rows`` reads them).  trace: None, or a TRACE int64 device tensor that the call adds to
-    (TRACE_NAMES).  _timed: (phase name, ev0, ev1) for tools/mesh_render_bench.py."""
+    (TRACE_NAMES).  _timed: (phase name, ev0, ev1) for tools/mesh_render_bench.py.  normals: None, or the (nv,3) fp32 vertex normals
+    of mesh_normals.vertex_normals; the result then gains normal (V,H,W,3) fp32, smooth (V,H,W) uint8 and normal_rgb (V,H,W,3) uint8
+    of mesh_normals.shade."""
     what = "mesh_render.render"
     nv, nf, H, W, cams, near, cull, bg = _arguments(verts, faces, rgb, cams, H, W, near, cull, background, what)
     V, dev = len(cams), verts.device
@@ -89,6 +91,9 @@ def render(verts, faces, rgb, cams, H, W, near=DEFAULT_NEAR, cull="none", backgr
         _lib.call("rcmvs_mr_render", *args, fusion._stream())
     else:
         _lib.call("rcmvs_mr_render_timed", *args, PHASES[_timed[0]], _timed[1], _timed[2], fusion._stream())
+    if normals is not None:
+        from . import mesh_normals
+        out.update(mesh_normals.shade(verts, faces, normals, cams, out["face"], near=near, background=background))
     return out
 
 
@@ -157,14 +162,16 @@ def sum_rows(rows, thresholds):
             "mean_abs": s / both if both else None}
 
 
-def render_views(verts, faces, rgb, views, out_dir=None, near=DEFAULT_NEAR, cull="none", thresholds=DEFAULT_THRESHOLDS, names=None, png=True):
+def render_views(verts, faces, rgb, views, out_dir=None, near=DEFAULT_NEAR, cull="none", thresholds=DEFAULT_THRESHOLDS, names=None, png=True,
+                 normals=None):
     """The hook of tsdf_mesh and eval_driver: the mesh into the cameras of ``views`` (tsdf_mesh.filtered_views' dict) at the size of
     its depth maps, compared with them -> the summed table with the summed counters as "stats".  out_dir: depth_mesh/<name>.pfm and
     render/<name>_shade.png, <name>_rgb.png are written there; the names default to the views' numbers in pair.txt (``views["ids"]``),
-    as the command line names them."""
+    as the command line names them.  normals: the vertex normals of mesh_normals.vertex_normals; render/<name>_smooth.png and
+    <name>_normal.png are written too."""
     depth = views["depth"]
     V, H, W = (int(s) for s in depth.shape)
-    out = render(verts, faces, rgb, views["cams"], H, W, near=near, cull=cull)
+    out = render(verts, faces, rgb, views["cams"], H, W, near=near, cull=cull, normals=normals)
     rows = compare(out["depth"], depth, thresholds)
     if out_dir is not None:
         write_views(out, out_dir, names if names is not None else ["{:0>8}".format(v) for v in views["ids"]], png)
@@ -184,6 +191,9 @@ def write_views(out, out_dir, names, png=True):
         if png:
             save_png(os.path.join(out_dir, "render", f"{name}_shade.png"), out["shade"][i])
             save_png(os.path.join(out_dir, "render", f"{name}_rgb.png"), out["rgb"][i])
+            if "smooth" in out:
+                save_png(os.path.join(out_dir, "render", f"{name}_smooth.png"), out["smooth"][i])
+                save_png(os.path.join(out_dir, "render", f"{name}_normal.png"), out["normal_rgb"][i])
 
 
 def main(argv=None):
@@ -200,6 +210,8 @@ def main(argv=None):
     ap.add_argument("--cull", choices=sorted(CULL), default="none")
     ap.add_argument("--thresholds", type=float, nargs="*", default=list(DEFAULT_THRESHOLDS))
     ap.add_argument("--no-png", action="store_true")
+    ap.add_argument("--normals", choices=("area", "sphere"), default=None, help="smooth shading: vertex normals of rc_mvsnet_amd.mesh_normals under this weight, "
+                                                                                "<view>_smooth.png and <view>_normal.png")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     dev = torch.device(a.device)
@@ -218,7 +230,11 @@ def main(argv=None):
         raise _lib.RcmvsError("mesh_render: give --size H W or --depth-folder (the size defaults to that of the first depth map)")
     v, f, c = dtu_io.read_ply_mesh_rgb(a.mesh)
     verts, faces, rgb = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (v.astype(np.float32), f.astype(np.int32), c.astype(np.uint8)))
-    out = render(verts, faces, rgb, cams, int(H), int(W), near=a.near, cull=a.cull)
+    normals = None
+    if a.normals is not None:
+        from . import mesh_normals
+        normals = mesh_normals.vertex_normals(verts, faces, a.normals)[0]
+    out = render(verts, faces, rgb, cams, int(H), int(W), near=a.near, cull=a.cull, normals=normals)
     write_views(out, a.out, names, png=not a.no_png)
     stats = stats_rows(out)
     total = {"views": len(names), "stats": {k: sum(s[k] for s in stats) for k in STAT_NAMES}}

@@ -27,7 +27,12 @@ nothing of it runs and the PLY and the summary are what they were.
 
 ``render_dir`` (``--render DIR``) renders the mesh just written into the views it was fused from (rc_mvsnet_amd.mesh_render), writes
 their depth PFMs and shade / colour PNGs under that folder, compares the rendered depth with the filtered depth maps still on the
-device and adds the summed table to the summary as "render".  Without it nothing of it runs."""
+device and adds the summed table to the summary as "render".  Without it nothing of it runs.
+
+``normals`` (``--normals area|sphere``) computes oriented per-vertex normals of the final mesh (rc_mvsnet_amd.mesh_normals), after
+the clean-up and the decimation: the PLY's vertex records become x y z nx ny nz red green blue, the summary gains the counters as
+"normals", and a render gains the smooth shade and the normal image.  Without it nothing of it runs and the PLY bytes are what
+they were."""
 import argparse
 import ctypes
 import json
@@ -255,18 +260,28 @@ class SparseTsdfVolume:
         return verts, faces, rgb
 
 
-def mesh_ply_bytes(verts, faces, rgb=None):
+def mesh_ply_bytes(verts, faces, rgb=None, normals=None):
     """Binary little-endian PLY of a triangle mesh: vertex properties x y z (float) red green blue (uchar), then ``element face``
-    with ``property list uchar int vertex_indices``.  rgb None: white.  dtu_io.read_ply_mesh reads it back exactly."""
+    with ``property list uchar int vertex_indices``.  rgb None: white.  normals (nv,3) fp32: the vertex record is x y z nx ny nz
+    (float) red green blue; without them the bytes are what they always were.  dtu_io.read_ply_mesh reads it back exactly, with
+    or without normals; dtu_io.read_ply_mesh_normals returns them too."""
     verts, faces = (t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in (verts, faces))
     rgb = None if rgb is None else (rgb.cpu().numpy() if torch.is_tensor(rgb) else np.asarray(rgb))
+    normals = None if normals is None else (normals.cpu().numpy() if torch.is_tensor(normals) else np.asarray(normals))
     nv, nf = len(verts), len(faces)
-    head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+    if normals is not None and (normals.dtype != np.float32 or normals.shape != (nv, 3)):
+        raise _lib.RcmvsError(f"mesh_ply_bytes: normals must be ({nv},3) float32")
+    extra = "" if normals is None else "property float nx\nproperty float ny\nproperty float nz\n"
+    head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
             "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %d\nproperty list uchar int vertex_indices\n"
-            "end_header\n" % (nv, nf)).encode("ascii")
-    vrec = np.empty(nv, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+            "end_header\n" % (nv, extra, nf)).encode("ascii")
+    vrec = np.empty(nv, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([] if normals is None else [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]) +
+                    [("red", "u1"), ("green", "u1"), ("blue", "u1")])
     for i, k in enumerate(("x", "y", "z")):
         vrec[k] = verts[:, i] if nv else 0
+    if normals is not None:
+        for i, k in enumerate(("nx", "ny", "nz")):
+            vrec[k] = normals[:, i] if nv else 0
     for i, k in enumerate(("red", "green", "blue")):
         vrec[k] = 255 if rgb is None else rgb[:, i]
     frec = np.empty(nf, dtype=[("n", "u1"), ("v", "<i4", (3,))])
@@ -369,7 +384,7 @@ def filtered_views_tanks(scan_folder, out_folder, geo_pixel_thres, geo_depth_thr
 def mesh_scan_tanks(scan_folder, out_folder, meshfilename, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes, geo_mask_thres,
                     n_views=None, scan="", device="cuda:0", depth_maps=None, conf_maps=None, voxel=None, resolution=1024, trunc_voxels=3.0,
                     min_weight=1, bounds=None, min_faces=0, min_fraction=0.0, keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0,
-                    render_dir=None):
+                    render_dir=None, normals=None):
     """The mesh counterpart of fusion.filter_depth_tanks, with its arguments: the scene's filtered ``depth_avg`` maps integrated into
     a SparseTsdfVolume (always sparse: these are the scenes a dense box does not fit) and meshed into ``meshfilename``.  Where no
     point survives the filter and no bounds are given there is nothing to put a grid round: the PLY is written empty, as
@@ -384,7 +399,7 @@ def mesh_scan_tanks(scan_folder, out_folder, meshfilename, geo_pixel_thres, geo_
                 "skipped_pixels": 0, "empty": "no point survives the filter"}
     return _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, True, device,
                        mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth, fill_holes), **_decimate_argument(decimate_cell, decimate_voxels),
-                       **_render_argument(render_dir))
+                       **_render_argument(render_dir), **_normals_argument(normals))
 
 
 def _decimate_argument(cell, voxels):
@@ -396,6 +411,13 @@ def _decimate_argument(cell, voxels):
 def _render_argument(render_dir):
     """-> the keyword that hands the folder of the rendered views to _mesh_views; nothing at all without one"""
     return {} if render_dir is None else {"render": str(render_dir)}
+
+
+def _normals_argument(weight):
+    """-> the keyword that hands mesh_normals.normals_options to _mesh_views; nothing at all when the option is not given"""
+    from . import mesh_normals
+    options = mesh_normals.normals_options(weight)
+    return {} if options is None else {"normals": options}
 
 
 def plan_grid(lo, hi, voxel=None, resolution=256, trunc_voxels=3.0, pad=True):
@@ -442,11 +464,13 @@ def plan_sparse_grid(lo, hi, voxel=None, resolution=1024, trunc_voxels=3.0, pad=
     return [float(v) for v in lo], voxel, bdims, trunc
 
 
-def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, sparse, device, clean=None, decimate=None, render=None):
+def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, sparse, device, clean=None, decimate=None, render=None,
+                normals=None):
     """Plans the grid, integrates the filtered views, extracts, cleans the mesh when ``clean`` (the keyword arguments of
     mesh_clean.clean_mesh) is given, then decimates it when ``decimate`` (of mesh_decimate.decimate_options) is given, and writes
     the PLY; with ``render`` (a folder) renders the written mesh into the views it was fused from (rc_mvsnet_amd.mesh_render) and
-    compares it with their filtered depth maps -> the summary dict"""
+    compares it with their filtered depth maps; with ``normals`` (of mesh_normals.normals_options) computes the vertex normals of
+    the final mesh, writes them into the PLY and hands them to the render -> the summary dict"""
     plan = plan_sparse_grid if sparse else plan_grid
     if bounds is not None:
         b = [float(v) for v in bounds]
@@ -475,11 +499,15 @@ def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight
         verts, faces, rgb, stats = mesh_decimate.decimate_mesh_path(verts, faces, rgb, decimate, voxel)
         extra["decimate"] = stats
     os.makedirs(os.path.dirname(os.path.abspath(meshfilename)), exist_ok=True)
+    vertex_normals = None
+    if normals is not None:
+        from . import mesh_normals
+        vertex_normals, extra["normals"] = mesh_normals.vertex_normals(verts, faces, normals["weight"])
     with open(meshfilename, "wb") as f:
-        f.write(mesh_ply_bytes(verts, faces, rgb))
+        f.write(mesh_ply_bytes(verts, faces, rgb, **({} if vertex_normals is None else {"normals": vertex_normals})))
     if render is not None:
         from . import mesh_render
-        extra["render"] = mesh_render.render_views(verts, faces, rgb, views, render)
+        extra["render"] = mesh_render.render_views(verts, faces, rgb, views, render, **({} if vertex_normals is None else {"normals": vertex_normals}))
     referenced = int(torch.unique(faces).numel())
     return dict({"mesh": meshfilename, "origin": origin, "dims": dims, "voxel": voxel, "trunc": trunc, "min_weight": int(min_weight),
                  "views": int(views["depth"].shape[0]), "vertices": int(verts.shape[0]), "faces": int(faces.shape[0]),
@@ -488,7 +516,7 @@ def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight
 
 def mesh_scan(pair_folder, scan_folder, out_folder, meshfilename, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage=3,
               voxel=None, resolution=256, trunc_voxels=3.0, min_weight=1, bounds=None, device="cuda:0", sparse=False, min_faces=0, min_fraction=0.0,
-              keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0, render_dir=None):
+              keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0, render_dir=None, normals=None):
     """Mesh one scan laid out as fusion.filter_depth reads it into ``meshfilename``.  bounds: (xmin, ymin, zmin, xmax, ymax, zmax),
     default the bounding box of the points that survive the filter, padded by the truncation distance.  sparse: a SparseTsdfVolume
     planned by plan_sparse_grid (resolution None: 1024); the summary then also reports bdims, active_blocks, allocated_voxels and
@@ -496,13 +524,15 @@ def mesh_scan(pair_folder, scan_folder, out_folder, meshfilename, prob_threshold
     extracted mesh and the summary gains its stats as "clean" (with fill_holes, "holes" among them).  decimate_cell (world units) or decimate_voxels (in voxels of the volume), not
     both: mesh_decimate.decimate runs after the clean-up and the summary gains its stats as "decimate".  render_dir: the written mesh is
     rendered into the views it was fused from (mesh_render.render_views: depth_mesh/ and render/ under that folder) and compared with
-    their filtered depth maps; the summary gains the summed table as "render".  Returns the summary dict."""
+    their filtered depth maps; the summary gains the summed table as "render".  normals ('area' or 'sphere'): mesh_normals.vertex_normals
+    runs last, on the mesh that is written; the PLY's vertex records gain nx ny nz, the summary gains the stats as "normals", and a
+    render gains the smooth shade and the normal image.  Returns the summary dict."""
     views = filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage, device)
     if resolution is None:
         resolution = 1024 if sparse else 256
     return _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, bool(sparse), device,
                        mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth, fill_holes), **_decimate_argument(decimate_cell, decimate_voxels),
-                       **_render_argument(render_dir))
+                       **_render_argument(render_dir), **_normals_argument(normals))
 
 
 def main(argv=None):
@@ -532,13 +562,15 @@ def main(argv=None):
     dec.add_argument("--decimate-voxels", type=float, default=0.0, help="decimation: edge of the clustering cells in voxels of the volume")
     ap.add_argument("--render", default=None, metavar="DIR", help="render the written mesh into the views it was fused from (rc_mvsnet_amd.mesh_render): "
                                                                   "DIR/depth_mesh/*.pfm, DIR/render/*.png, and \"render\" in the summary")
+    ap.add_argument("--normals", choices=("area", "sphere"), default=None, help="write oriented vertex normals (rc_mvsnet_amd.mesh_normals) into the PLY; "
+                                                                                "with --render also <view>_smooth.png and <view>_normal.png")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     summary = mesh_scan(a.pair_folder, a.scan_folder, a.out_folder, a.mesh, a.prob_thres, a.num_consistency, a.img_dist_thres, a.depth_thres,
                         num_stage=a.num_stage, voxel=a.voxel, resolution=a.resolution, trunc_voxels=a.trunc_voxels, min_weight=a.min_weight,
                         bounds=a.bounds, device=a.device, sparse=a.sparse, min_faces=a.min_faces, min_fraction=a.min_fraction,
                         keep_largest=a.keep_largest, smooth=a.smooth, decimate_cell=a.decimate_cell, decimate_voxels=a.decimate_voxels,
-                        fill_holes=a.fill_holes, render_dir=a.render)
+                        fill_holes=a.fill_holes, render_dir=a.render, normals=a.normals)
     print(json.dumps(summary))
     return summary
 
