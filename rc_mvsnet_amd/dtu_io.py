@@ -133,6 +133,71 @@ def _ascii_rows(tokens, pos, count, props, path, what):
     return rows, pos
 
 
+def _fixed_face_records(f, count, props, end):
+    """A binary element whose list properties have the same lengths in every record, read at once -> the records (list i: its count
+    as "n<i>", its items as "l<i>"; scalar i as "p<i>"), the file left after the element; None, the file where it was, when the
+    lengths differ or the data is short.  The lengths are those of the first record."""
+    here = f.tell()
+    fields = []
+    for i, (_, t) in enumerate(props):
+        if isinstance(t, tuple):
+            cdt, idt = np.dtype(t[1]).newbyteorder(end), np.dtype(t[2]).newbyteorder(end)
+            b = f.read(cdt.itemsize)
+            if len(b) != cdt.itemsize:
+                f.seek(here)
+                return None
+            k = int(np.frombuffer(b, dtype=cdt)[0])
+            f.seek(k * idt.itemsize, 1)
+            fields += [(f"n{i}", cdt), (f"l{i}", idt, (k,))]
+        else:
+            fields.append((f"p{i}", np.dtype(t).newbyteorder(end)))
+            f.seek(fields[-1][1].itemsize, 1)
+    dt = np.dtype(fields)
+    f.seek(here)
+    buf = f.read(dt.itemsize * count)
+    if len(buf) == dt.itemsize * count:
+        rec = np.frombuffer(buf, dtype=dt)
+        if all(bool((rec[name] == rec[name][0]).all()) for name, *_ in fields if name[0] == "n"):
+            return rec
+    f.seek(here)
+    return None
+
+
+def read_ply_mesh_texture(path):
+    """read_ply_mesh_normals plus the per-face texture coordinates of a PLY that tsdf_mesh.mesh_ply_bytes wrote with ``texcoords``
+    -> (verts, faces, rgb or None, normals or None, texcoords (m,3,2) float32 with their bits as stored or None, the name after
+    ``comment TextureFile`` or None).  The coordinates are the face element's list ``texcoord`` of six floats per face (binary
+    files); anything else gives None."""
+    verts, faces, rgb, nrm = _read_ply_mesh(path, True, True)
+    uv, name = None, None
+    with open(path, "rb") as f:
+        for line in f:
+            tok = line.decode("ascii", "replace").split()
+            if tok[:2] == ["comment", "TextureFile"] and len(tok) == 3:
+                name = tok[2]
+            if tok[:1] == ["end_header"]:
+                break
+        f.seek(0)
+        fmt, elements = _ply_header(f)
+        names = [e[0] for e in elements]
+        face_name = next((k for k in _FACE_ELEMENTS if k in names), None)
+        if fmt != "ascii" and face_name is not None:
+            end = "<" if fmt == "binary_little_endian" else ">"
+            for ename, count, props in elements:
+                if ename != face_name:
+                    _skip_binary_element(f, count, props, end)
+                    continue
+                at = next((i for i, (p, t) in enumerate(props) if p == "texcoord" and isinstance(t, tuple) and np.dtype(t[2]) == np.float32), None)
+                if at is not None and count:
+                    rec = _fixed_face_records(f, count, props, end)
+                    if rec is not None and rec[f"n{at}"][0] == 6:
+                        uv = rec[f"l{at}"].astype("<f4").astype(np.float32).reshape(count, 3, 2)
+                elif at is not None:
+                    uv = np.zeros((0, 3, 2), np.float32)
+                break
+    return verts, faces, rgb, nrm, uv, name
+
+
 def _binary_faces(f, count, props, idx, end, path):
     """-> (count, 3) int64 indices of a binary face element; a single list property with 3 indices per face is read at once"""
     lists = [i for i, (_, t) in enumerate(props) if isinstance(t, tuple)]
@@ -153,6 +218,12 @@ def _binary_faces(f, count, props, idx, end, path):
         if k is not None:
             raise FormatError(f"{path}: face {k} has {int(rec['n'][k])} vertices (only triangles are supported)")
         f.seek(here)
+    elif count:
+        rec = _fixed_face_records(f, count, props, end)              # several lists (a textured PLY's texcoord): every face the same lengths
+        if rec is not None:
+            if int(rec[f"n{idx}"][0]) != 3:
+                raise FormatError(f"{path}: face 0 has {int(rec[f'n{idx}'][0])} vertices (only triangles are supported)")
+            return rec[f"l{idx}"].astype(np.int64)
     out = np.empty((count, 3), dtype=np.int64)
     for r in range(count):
         for i, (_, t) in enumerate(props):

@@ -130,7 +130,7 @@ def run_scans(model, args, device, rank, world):
                                               min_fraction=args.mesh_min_fraction, keep_largest=args.mesh_keep_largest, smooth=args.mesh_smooth,
                                               decimate_voxels=args.mesh_decimate_voxels, fill_holes=args.mesh_fill_holes,
                                               render_dir=None if args.mesh_render is None else os.path.join(args.mesh_render, scan),
-                                              normals=args.mesh_normals)
+                                              normals=args.mesh_normals, **({"texture": True} if args.mesh_texture else {}))
                 print(json.dumps(summary))
             if args.dtu_gt:
                 score_scan(args, scan, device)
@@ -223,7 +223,7 @@ def run_tanks(model, args, device, rank, world):
                                                 keep_largest=args.mesh_keep_largest, smooth=args.mesh_smooth,
                                                 decimate_voxels=args.mesh_decimate_voxels, fill_holes=args.mesh_fill_holes,
                                                 render_dir=None if args.mesh_render is None else os.path.join(args.mesh_render, scene),
-                                                normals=args.mesh_normals)
+                                                normals=args.mesh_normals, **({"texture": True} if args.mesh_texture else {}))
             print(json.dumps(summary))
         del depth_maps, conf_maps
     if times:
@@ -284,6 +284,9 @@ def main(argv=None):
     ap.add_argument("--mesh-normals", choices=("area", "sphere"), default=None,
                     help="--mesh: write oriented vertex normals (rc_mvsnet_amd.mesh_normals) of the final mesh into the PLY; with --mesh-render "
                          "also the smooth shade and the normal image")
+    ap.add_argument("--mesh-texture", action="store_true",
+                    help="--mesh: texture the final mesh from the views' images (rc_mvsnet_amd.mesh_texture): texcoords in the PLY, the atlas next "
+                         "to it as <name>.png; with --mesh-render also the textured views")
     ap.add_argument("--mesh-decimate-voxels", type=float, default=0.0,
                     help="--mesh: decimation (rc_mvsnet_amd.mesh_decimate) after the clean-up, cells of this many voxels")
     ap.add_argument("--dtu-gt", default=None, help="DTU MVS_Data folder: after --filter, score each fused cloud (accuracy / completeness, "

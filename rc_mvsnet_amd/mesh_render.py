@@ -12,8 +12,8 @@ visibility by a 64-bit integer minimum of (depth bits, face number): every outpu
         --depth-folder out/scan9
 
 Limits: no near-plane clipping (a face with a vertex nearer than ``near`` or more than 2^16 pixels from the image origin is dropped
-and counted as clipped); one sample per pixel, no anti-aliasing; the shade is flat, with a light at the camera; vertex colours only, no
-texture; smooth shading only with ``normals`` (``--normals``); H, W <= 16384; pinhole cameras only.  No CPU fallback."""
+and counted as clipped); one sample per pixel, no anti-aliasing; the shade is flat, with a light at the camera; vertex colours unless
+``texture`` is given (``--texture``, for a PLY with texcoords); smooth shading only with ``normals`` (``--normals``); H, W <= 16384; pinhole cameras only.  No CPU fallback."""
 import argparse
 import ctypes
 import json
@@ -62,7 +62,7 @@ def _arguments(verts, faces, rgb, cams, H, W, near, cull, background, what):
     return nv, nf, H, W, cams, near, CULL[cull], bg[0] | bg[1] << 8 | bg[2] << 16
 
 
-def render(verts, faces, rgb, cams, H, W, near=DEFAULT_NEAR, cull="none", background=(0, 0, 0), trace=None, _timed=None, normals=None):
+def render(verts, faces, rgb, cams, H, W, near=DEFAULT_NEAR, cull="none", background=(0, 0, 0), trace=None, _timed=None, normals=None, texture=None):
     """verts (nv,3) fp32, faces (nf,3) int32, rgb (nv,3) uint8 or None on the device; cams (V,16) float64 on the host, the rows of
     tsdf_mesh.camera_row; cull 'none' or 'back' (back: only faces whose normal (b - a) x (c - a) points at the camera, which is how
     the extracted meshes are oriented) -> dict of device tensors: depth (V,H,W) fp32 (0 where no face is seen), face (V,H,W) int32
@@ -71,7 +71,8 @@ def render(verts, faces, rgb, cams, H, W, near=DEFAULT_NEAR, cull="none", backgr
     STAT_NAMES per view (``stats_rows`` reads them).  trace: None, or a TRACE int64 device tensor that the call adds to
     (TRACE_NAMES).  _timed: (phase name, ev0, ev1) for tools/mesh_render_bench.py.  normals: None, or the (nv,3) fp32 vertex normals
     of mesh_normals.vertex_normals; the result then gains normal (V,H,W,3) fp32, smooth (V,H,W) uint8 and normal_rgb (V,H,W,3) uint8
-    of mesh_normals.shade."""
+    of mesh_normals.shade.  texture: None, or (atlas (Sy,S,3) uint8, texel (nf,3,2) int32) of mesh_texture.texture; the result then gains
+    tex_rgb (V,H,W,3) uint8 of mesh_texture.shade."""
     what = "mesh_render.render"
     nv, nf, H, W, cams, near, cull, bg = _arguments(verts, faces, rgb, cams, H, W, near, cull, background, what)
     V, dev = len(cams), verts.device
@@ -94,6 +95,9 @@ def render(verts, faces, rgb, cams, H, W, near=DEFAULT_NEAR, cull="none", backgr
     if normals is not None:
         from . import mesh_normals
         out.update(mesh_normals.shade(verts, faces, normals, cams, out["face"], near=near, background=background))
+    if texture is not None:
+        from . import mesh_texture
+        out["tex_rgb"] = mesh_texture.shade(verts, faces, cams, out["face"], texture[1], texture[0], near=near, background=background)
     return out
 
 
@@ -163,21 +167,24 @@ def sum_rows(rows, thresholds):
 
 
 def render_views(verts, faces, rgb, views, out_dir=None, near=DEFAULT_NEAR, cull="none", thresholds=DEFAULT_THRESHOLDS, names=None, png=True,
-                 normals=None):
+                 normals=None, texture=None):
     """The hook of tsdf_mesh and eval_driver: the mesh into the cameras of ``views`` (tsdf_mesh.filtered_views' dict) at the size of
     its depth maps, compared with them -> the summed table with the summed counters as "stats".  out_dir: depth_mesh/<name>.pfm and
     render/<name>_shade.png, <name>_rgb.png are written there; the names default to the views' numbers in pair.txt (``views["ids"]``),
     as the command line names them.  normals: the vertex normals of mesh_normals.vertex_normals; render/<name>_smooth.png and
-    <name>_normal.png are written too."""
+    <name>_normal.png are written too.  texture: (atlas, texel) of mesh_texture.texture; render/<name>_tex.png is written too and the
+    result gains "textured_views"."""
     depth = views["depth"]
     V, H, W = (int(s) for s in depth.shape)
-    out = render(verts, faces, rgb, views["cams"], H, W, near=near, cull=cull, normals=normals)
+    out = render(verts, faces, rgb, views["cams"], H, W, near=near, cull=cull, normals=normals, texture=texture)
     rows = compare(out["depth"], depth, thresholds)
     if out_dir is not None:
         write_views(out, out_dir, names if names is not None else ["{:0>8}".format(v) for v in views["ids"]], png)
     total = sum_rows(rows, thresholds)
     stats = stats_rows(out)
     total["stats"] = {k: sum(s[k] for s in stats) for k in STAT_NAMES}
+    if texture is not None:
+        total["textured_views"] = V
     return total
 
 
@@ -194,6 +201,8 @@ def write_views(out, out_dir, names, png=True):
             if "smooth" in out:
                 save_png(os.path.join(out_dir, "render", f"{name}_smooth.png"), out["smooth"][i])
                 save_png(os.path.join(out_dir, "render", f"{name}_normal.png"), out["normal_rgb"][i])
+            if "tex_rgb" in out:
+                save_png(os.path.join(out_dir, "render", f"{name}_tex.png"), out["tex_rgb"][i])
 
 
 def main(argv=None):
@@ -212,6 +221,7 @@ def main(argv=None):
     ap.add_argument("--no-png", action="store_true")
     ap.add_argument("--normals", choices=("area", "sphere"), default=None, help="smooth shading: vertex normals of rc_mvsnet_amd.mesh_normals under this weight, "
                                                                                 "<view>_smooth.png and <view>_normal.png")
+    ap.add_argument("--texture", action="store_true", help="the PLY has texcoords (rc_mvsnet_amd.mesh_texture) and its atlas lies next to it: <view>_tex.png")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     dev = torch.device(a.device)
@@ -234,7 +244,11 @@ def main(argv=None):
     if a.normals is not None:
         from . import mesh_normals
         normals = mesh_normals.vertex_normals(verts, faces, a.normals)[0]
-    out = render(verts, faces, rgb, cams, int(H), int(W), near=a.near, cull=a.cull, normals=normals)
+    texture = None
+    if a.texture:
+        from . import mesh_texture
+        texture = mesh_texture.read_textured(a.mesh, dev)[3:]
+    out = render(verts, faces, rgb, cams, int(H), int(W), near=a.near, cull=a.cull, normals=normals, texture=texture)
     write_views(out, a.out, names, png=not a.no_png)
     stats = stats_rows(out)
     total = {"views": len(names), "stats": {k: sum(s[k] for s in stats) for k in STAT_NAMES}}

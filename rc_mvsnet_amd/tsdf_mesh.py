@@ -32,7 +32,12 @@ device and adds the summed table to the summary as "render".  Without it nothing
 ``normals`` (``--normals area|sphere``) computes oriented per-vertex normals of the final mesh (rc_mvsnet_amd.mesh_normals), after
 the clean-up and the decimation: the PLY's vertex records become x y z nx ny nz red green blue, the summary gains the counters as
 "normals", and a render gains the smooth shade and the normal image.  Without it nothing of it runs and the PLY bytes are what
-they were."""
+they were.
+
+``texture`` (``--texture [--texture-size N]``) textures the final mesh from the images and cameras of the views it was fused from
+(rc_mvsnet_amd.mesh_texture), last of all: the PLY's faces gain six texture coordinates each and the header names the atlas, which is
+written next to the PLY as <name>.png; the summary gains the counters and the atlas size as "texture", and a render gains the
+textured views.  Without it nothing of it runs and the PLY bytes are what they were."""
 import argparse
 import ctypes
 import json
@@ -260,21 +265,33 @@ class SparseTsdfVolume:
         return verts, faces, rgb
 
 
-def mesh_ply_bytes(verts, faces, rgb=None, normals=None):
+def mesh_ply_bytes(verts, faces, rgb=None, normals=None, texcoords=None, texture_file=None):
     """Binary little-endian PLY of a triangle mesh: vertex properties x y z (float) red green blue (uchar), then ``element face``
     with ``property list uchar int vertex_indices``.  rgb None: white.  normals (nv,3) fp32: the vertex record is x y z nx ny nz
     (float) red green blue; without them the bytes are what they always were.  dtu_io.read_ply_mesh reads it back exactly, with
-    or without normals; dtu_io.read_ply_mesh_normals returns them too."""
+    or without normals; dtu_io.read_ply_mesh_normals returns them too.  texcoords (nf,3,2) fp32 (mesh_texture's "uv"): the header gains
+    ``comment TextureFile <texture_file>`` and the face element a second property ``property list uchar float texcoord`` with the six
+    floats u v of the corners a, b, c, the convention MeshLab reads; dtu_io.read_ply_mesh_texture returns them."""
     verts, faces = (t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in (verts, faces))
     rgb = None if rgb is None else (rgb.cpu().numpy() if torch.is_tensor(rgb) else np.asarray(rgb))
     normals = None if normals is None else (normals.cpu().numpy() if torch.is_tensor(normals) else np.asarray(normals))
     nv, nf = len(verts), len(faces)
     if normals is not None and (normals.dtype != np.float32 or normals.shape != (nv, 3)):
         raise _lib.RcmvsError(f"mesh_ply_bytes: normals must be ({nv},3) float32")
+    if texcoords is not None:
+        texcoords = np.asarray(texcoords)
+        if texcoords.dtype != np.float32 or texcoords.shape != (nf, 3, 2):
+            raise _lib.RcmvsError(f"mesh_ply_bytes: texcoords must be ({nf},3,2) float32")
+        if not isinstance(texture_file, str) or not texture_file or any(ch.isspace() or not ch.isascii() for ch in texture_file):
+            raise _lib.RcmvsError(f"mesh_ply_bytes: texture_file = {texture_file!r} (the atlas's file name, ASCII without spaces, goes with texcoords)")
+    elif texture_file is not None:
+        raise _lib.RcmvsError("mesh_ply_bytes: texture_file without texcoords")
     extra = "" if normals is None else "property float nx\nproperty float ny\nproperty float nz\n"
-    head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
-            "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %d\nproperty list uchar int vertex_indices\n"
-            "end_header\n" % (nv, extra, nf)).encode("ascii")
+    comment = "" if texcoords is None else "comment TextureFile %s\n" % texture_file
+    fextra = "" if texcoords is None else "property list uchar float texcoord\n"
+    head = ("ply\nformat binary_little_endian 1.0\n%selement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %d\nproperty list uchar int vertex_indices\n%s"
+            "end_header\n" % (comment, nv, extra, nf, fextra)).encode("ascii")
     vrec = np.empty(nv, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([] if normals is None else [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]) +
                     [("red", "u1"), ("green", "u1"), ("blue", "u1")])
     for i, k in enumerate(("x", "y", "z")):
@@ -284,9 +301,12 @@ def mesh_ply_bytes(verts, faces, rgb=None, normals=None):
             vrec[k] = normals[:, i] if nv else 0
     for i, k in enumerate(("red", "green", "blue")):
         vrec[k] = 255 if rgb is None else rgb[:, i]
-    frec = np.empty(nf, dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    frec = np.empty(nf, dtype=[("n", "u1"), ("v", "<i4", (3,))] + ([] if texcoords is None else [("m", "u1"), ("t", "<f4", (6,))]))
     frec["n"] = 3
     frec["v"] = faces.reshape(nf, 3)
+    if texcoords is not None:
+        frec["m"] = 6
+        frec["t"] = texcoords.reshape(nf, 6)
     return head + vrec.tobytes() + frec.tobytes()
 
 
@@ -384,7 +404,7 @@ def filtered_views_tanks(scan_folder, out_folder, geo_pixel_thres, geo_depth_thr
 def mesh_scan_tanks(scan_folder, out_folder, meshfilename, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes, geo_mask_thres,
                     n_views=None, scan="", device="cuda:0", depth_maps=None, conf_maps=None, voxel=None, resolution=1024, trunc_voxels=3.0,
                     min_weight=1, bounds=None, min_faces=0, min_fraction=0.0, keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0,
-                    render_dir=None, normals=None):
+                    render_dir=None, normals=None, texture=False, texture_size=None):
     """The mesh counterpart of fusion.filter_depth_tanks, with its arguments: the scene's filtered ``depth_avg`` maps integrated into
     a SparseTsdfVolume (always sparse: these are the scenes a dense box does not fit) and meshed into ``meshfilename``.  Where no
     point survives the filter and no bounds are given there is nothing to put a grid round: the PLY is written empty, as
@@ -399,7 +419,7 @@ def mesh_scan_tanks(scan_folder, out_folder, meshfilename, geo_pixel_thres, geo_
                 "skipped_pixels": 0, "empty": "no point survives the filter"}
     return _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, True, device,
                        mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth, fill_holes), **_decimate_argument(decimate_cell, decimate_voxels),
-                       **_render_argument(render_dir), **_normals_argument(normals))
+                       **_render_argument(render_dir), **_normals_argument(normals), **_texture_argument(texture, texture_size))
 
 
 def _decimate_argument(cell, voxels):
@@ -418,6 +438,14 @@ def _normals_argument(weight):
     from . import mesh_normals
     options = mesh_normals.normals_options(weight)
     return {} if options is None else {"normals": options}
+
+
+def _texture_argument(enabled, max_size):
+    """-> the keyword that hands mesh_texture.texture_options to _mesh_views; nothing at all when the option is not given"""
+    if not enabled:
+        return {}
+    from . import mesh_texture
+    return {"texture": mesh_texture.texture_options(True, max_size)}
 
 
 def plan_grid(lo, hi, voxel=None, resolution=256, trunc_voxels=3.0, pad=True):
@@ -465,12 +493,14 @@ def plan_sparse_grid(lo, hi, voxel=None, resolution=1024, trunc_voxels=3.0, pad=
 
 
 def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, sparse, device, clean=None, decimate=None, render=None,
-                normals=None):
+                normals=None, texture=None):
     """Plans the grid, integrates the filtered views, extracts, cleans the mesh when ``clean`` (the keyword arguments of
     mesh_clean.clean_mesh) is given, then decimates it when ``decimate`` (of mesh_decimate.decimate_options) is given, and writes
     the PLY; with ``render`` (a folder) renders the written mesh into the views it was fused from (rc_mvsnet_amd.mesh_render) and
     compares it with their filtered depth maps; with ``normals`` (of mesh_normals.normals_options) computes the vertex normals of
-    the final mesh, writes them into the PLY and hands them to the render -> the summary dict"""
+    the final mesh, writes them into the PLY and hands them to the render; with ``texture`` (of mesh_texture.texture_options) textures
+    the final mesh from the views' images and cameras, writes the texcoords into the PLY and the atlas next to it as <name>.png, and
+    hands both to the render -> the summary dict"""
     plan = plan_sparse_grid if sparse else plan_grid
     if bounds is not None:
         b = [float(v) for v in bounds]
@@ -503,11 +533,22 @@ def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight
     if normals is not None:
         from . import mesh_normals
         vertex_normals, extra["normals"] = mesh_normals.vertex_normals(verts, faces, normals["weight"])
+    ply_extra = {} if vertex_normals is None else {"normals": vertex_normals}            # the keywords of mesh_ply_bytes and of render_views: none without an option
+    render_extra = dict(ply_extra)
+    if texture is not None:
+        from . import mesh_texture
+        from .depth_vis import save_png
+        tex = mesh_texture.texture(verts, faces, rgb, views["rgb"], views["cams"], **texture)
+        stem = os.path.splitext(os.path.abspath(meshfilename))[0]
+        save_png(stem + ".png", tex["atlas"])
+        ply_extra.update(texcoords=tex["uv"], texture_file=os.path.basename(stem) + ".png")
+        render_extra["texture"] = (tex["atlas"], tex["texel"])
+        extra["texture"] = dict(mesh_texture.summary(tex), file=stem + ".png")
     with open(meshfilename, "wb") as f:
-        f.write(mesh_ply_bytes(verts, faces, rgb, **({} if vertex_normals is None else {"normals": vertex_normals})))
+        f.write(mesh_ply_bytes(verts, faces, rgb, **ply_extra))
     if render is not None:
         from . import mesh_render
-        extra["render"] = mesh_render.render_views(verts, faces, rgb, views, render, **({} if vertex_normals is None else {"normals": vertex_normals}))
+        extra["render"] = mesh_render.render_views(verts, faces, rgb, views, render, **render_extra)
     referenced = int(torch.unique(faces).numel())
     return dict({"mesh": meshfilename, "origin": origin, "dims": dims, "voxel": voxel, "trunc": trunc, "min_weight": int(min_weight),
                  "views": int(views["depth"].shape[0]), "vertices": int(verts.shape[0]), "faces": int(faces.shape[0]),
@@ -516,7 +557,8 @@ def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight
 
 def mesh_scan(pair_folder, scan_folder, out_folder, meshfilename, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage=3,
               voxel=None, resolution=256, trunc_voxels=3.0, min_weight=1, bounds=None, device="cuda:0", sparse=False, min_faces=0, min_fraction=0.0,
-              keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0, render_dir=None, normals=None):
+              keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0, render_dir=None, normals=None, texture=False,
+              texture_size=None):
     """Mesh one scan laid out as fusion.filter_depth reads it into ``meshfilename``.  bounds: (xmin, ymin, zmin, xmax, ymax, zmax),
     default the bounding box of the points that survive the filter, padded by the truncation distance.  sparse: a SparseTsdfVolume
     planned by plan_sparse_grid (resolution None: 1024); the summary then also reports bdims, active_blocks, allocated_voxels and
@@ -526,13 +568,15 @@ def mesh_scan(pair_folder, scan_folder, out_folder, meshfilename, prob_threshold
     rendered into the views it was fused from (mesh_render.render_views: depth_mesh/ and render/ under that folder) and compared with
     their filtered depth maps; the summary gains the summed table as "render".  normals ('area' or 'sphere'): mesh_normals.vertex_normals
     runs last, on the mesh that is written; the PLY's vertex records gain nx ny nz, the summary gains the stats as "normals", and a
-    render gains the smooth shade and the normal image.  Returns the summary dict."""
+    render gains the smooth shade and the normal image.  texture: mesh_texture.texture runs last, on the mesh that is written, from the
+    views' images and cameras (texture_size: the atlas's largest side, default 8192); the PLY's faces gain texcoords, the atlas is written
+    next to it as <name>.png, the summary gains "texture", and a render gains the textured views.  Returns the summary dict."""
     views = filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage, device)
     if resolution is None:
         resolution = 1024 if sparse else 256
     return _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, bool(sparse), device,
                        mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth, fill_holes), **_decimate_argument(decimate_cell, decimate_voxels),
-                       **_render_argument(render_dir), **_normals_argument(normals))
+                       **_render_argument(render_dir), **_normals_argument(normals), **_texture_argument(texture, texture_size))
 
 
 def main(argv=None):
@@ -564,13 +608,16 @@ def main(argv=None):
                                                                   "DIR/depth_mesh/*.pfm, DIR/render/*.png, and \"render\" in the summary")
     ap.add_argument("--normals", choices=("area", "sphere"), default=None, help="write oriented vertex normals (rc_mvsnet_amd.mesh_normals) into the PLY; "
                                                                                 "with --render also <view>_smooth.png and <view>_normal.png")
+    ap.add_argument("--texture", action="store_true", help="texture the written mesh from the views' images (rc_mvsnet_amd.mesh_texture): texcoords in the "
+                                                           "PLY, the atlas next to it as <name>.png; with --render also <view>_tex.png")
+    ap.add_argument("--texture-size", type=int, default=None, metavar="N", help="the atlas's largest side (default 8192, at most 16384)")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     summary = mesh_scan(a.pair_folder, a.scan_folder, a.out_folder, a.mesh, a.prob_thres, a.num_consistency, a.img_dist_thres, a.depth_thres,
                         num_stage=a.num_stage, voxel=a.voxel, resolution=a.resolution, trunc_voxels=a.trunc_voxels, min_weight=a.min_weight,
                         bounds=a.bounds, device=a.device, sparse=a.sparse, min_faces=a.min_faces, min_fraction=a.min_fraction,
                         keep_largest=a.keep_largest, smooth=a.smooth, decimate_cell=a.decimate_cell, decimate_voxels=a.decimate_voxels,
-                        fill_holes=a.fill_holes, render_dir=a.render, normals=a.normals)
+                        fill_holes=a.fill_holes, render_dir=a.render, normals=a.normals, **({"texture": True, "texture_size": a.texture_size} if a.texture else {}))
     print(json.dumps(summary))
     return summary
 
