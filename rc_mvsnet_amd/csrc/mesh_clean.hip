@@ -21,7 +21,7 @@
 #include "common.h"
 #include "mesh_clean.h"
 #include "mesh_clean_math.h"
-#include "scan_sort.h"                                            // scan3, zero_u64_kernel
+#include "scan_sort.h"                                            // gid, blocks, scan3, zero_kernel
 #include "tsdf_mesh_cells.h"                                      // tm_block_sum (256 threads)
 
 #pragma clang fp contract(off)
@@ -31,17 +31,15 @@ namespace rcmvs {
 constexpr int MC_BLOCK = TM_BLOCK;
 constexpr int MC_LIMIT = RCMVS_MC_SORT_LIMIT;
 constexpr int MC_HEAVY_GRID = 64;
-static_assert(MC_BLOCK == SS_BLOCK, "zero_u64_kernel is launched with this family's block");
+static_assert(MC_BLOCK == SS_BLOCK, "gid, blocks and zero_kernel count in this family's block");
 static_assert(RCMVS_MC_SCAN_TILE == SS_TILE && RCMVS_MC_SCAN_WORK == SS_WORK, "mesh_clean.h describes scan_sort.h's work area");
 static_assert(MC_LIMIT * MC_BLOCK * 4 <= 64 * 1024, "the lanes' segments share one block's static LDS");
 
 using u64 = unsigned long long;
 
-__device__ inline long long mc_id() { return (long long)blockIdx.x * MC_BLOCK + threadIdx.x; }
-
 // ---- components ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MC_BLOCK) void mc_init_kernel(int* __restrict__ label, int* __restrict__ comp_faces, int nv, u64* __restrict__ counts) {
-    const long long v = mc_id();
+    const long long v = gid();
     if (v < nv) { label[v] = (int)v; comp_faces[v] = 0; }
     if (v < 4) counts[v] = 0;
 }
@@ -77,7 +75,7 @@ __device__ inline void mc_unite(int* parent, int a, int b) {
 
 __global__ __launch_bounds__(MC_BLOCK) void mc_hook_kernel(const int* __restrict__ faces, int nv, int nf, int* parent, unsigned char* __restrict__ face_ok,
                                                            u64* counts) {
-    const long long f = mc_id();
+    const long long f = gid();
     if (f >= nf) return;
     const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
     const bool ok = mc::face_valid(a, b, c, nv);
@@ -88,7 +86,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_hook_kernel(const int* __restrict
 }
 
 __global__ __launch_bounds__(MC_BLOCK) void mc_flatten_kernel(int* parent, int nv) {
-    const long long v = mc_id();
+    const long long v = gid();
     if (v >= nv) return;
     volatile int* p = parent;
     int r = (int)v, n;
@@ -98,7 +96,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_flatten_kernel(int* parent, int n
 
 __global__ __launch_bounds__(MC_BLOCK) void mc_face_count_kernel(const int* __restrict__ faces, const unsigned char* __restrict__ face_ok, int nf,
                                                                  const int* __restrict__ label, int* comp_faces) {
-    const long long f = mc_id();
+    const long long f = gid();
     if (f >= nf || !face_ok[f]) return;
     atomicAdd(&comp_faces[label[faces[3 * f]]], 1);
 }
@@ -107,7 +105,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_face_count_kernel(const int* __re
 __global__ __launch_bounds__(MC_BLOCK) void mc_root_flag_kernel(const int* __restrict__ label, const int* __restrict__ comp_faces, int nv,
                                                                 unsigned char* __restrict__ flags, u64* totals) {
     __shared__ unsigned sh[MC_BLOCK];
-    const long long v = mc_id();
+    const long long v = gid();
     unsigned most = 0;
     if (v < nv) {
         const bool row = label[v] == (int)v && comp_faces[v] > 0;
@@ -125,7 +123,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_root_flag_kernel(const int* __res
 
 __global__ __launch_bounds__(MC_BLOCK) void mc_table_kernel(const int* __restrict__ comp_faces, int nv, const unsigned char* __restrict__ flags,
                                                             const int* __restrict__ rank, int* __restrict__ table, int capacity) {
-    const long long v = mc_id();
+    const long long v = gid();
     if (v >= nv || !flags[v]) return;
     const int r = rank[v];
     if (r < 0 || r >= capacity) return;
@@ -137,7 +135,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_table_kernel(const int* __restric
 __global__ __launch_bounds__(MC_BLOCK) void mc_vert_init_kernel(const int* __restrict__ label, const int* __restrict__ comp_faces, int nv, mc::Select sel,
                                                                 int drop, unsigned char* __restrict__ vert_keep, u64* totals) {
     __shared__ unsigned sh[MC_BLOCK];
-    const long long v = mc_id();
+    const long long v = gid();
     unsigned kept = 0;
     if (v < nv) {
         vert_keep[v] = drop ? 0 : 1;
@@ -150,7 +148,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_vert_init_kernel(const int* __res
 __global__ __launch_bounds__(MC_BLOCK) void mc_face_keep_kernel(const int* __restrict__ faces, const unsigned char* __restrict__ face_ok,
                                                                 const int* __restrict__ label, const int* __restrict__ comp_faces, int nv, int nf,
                                                                 mc::Select sel, int drop, unsigned char* __restrict__ face_keep, unsigned char* vert_keep) {
-    const long long f = mc_id();
+    const long long f = gid();
     if (f >= nf) return;
     const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
     bool keep = face_ok[f] && mc::face_valid(a, b, c, nv);
@@ -166,7 +164,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_face_keep_kernel(const int* __res
 __global__ __launch_bounds__(MC_BLOCK) void mc_gather_verts_kernel(const unsigned* __restrict__ verts, const unsigned char* __restrict__ rgb,
                                                                    const unsigned char* __restrict__ vert_keep, const int* __restrict__ vert_rank, int nv,
                                                                    int nv_out, unsigned* __restrict__ out_verts, unsigned char* __restrict__ out_rgb) {
-    const long long v = mc_id();
+    const long long v = gid();
     if (v >= nv || !vert_keep[v]) return;
     const int r = vert_rank[v];
     if (r < 0 || r >= nv_out) return;
@@ -181,7 +179,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_gather_verts_kernel(const unsigne
 __global__ __launch_bounds__(MC_BLOCK) void mc_gather_faces_kernel(const int* __restrict__ faces, const unsigned char* __restrict__ face_keep,
                                                                    const int* __restrict__ face_rank, const int* __restrict__ vert_rank, int nv, int nf,
                                                                    int nf_out, int* __restrict__ out_faces) {
-    const long long f = mc_id();
+    const long long f = gid();
     if (f >= nf || !face_keep[f]) return;
     const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
     const int r = face_rank[f];
@@ -193,13 +191,13 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_gather_faces_kernel(const int* __
 
 // ---- adjacency ----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MC_BLOCK) void mc_zero_int_kernel(int* __restrict__ p, int n, u64* __restrict__ stats) {
-    const long long i = mc_id();
+    const long long i = gid();
     if (i < n) p[i] = 0;
     if (i < 6) stats[i] = 0;
 }
 
 __global__ __launch_bounds__(MC_BLOCK) void mc_degree_kernel(const int* __restrict__ faces, int nv, int nf, int* cursor) {
-    const long long f = mc_id();
+    const long long f = gid();
     if (f >= nf) return;
     const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
     if (!mc::face_valid(a, b, c, nv)) return;
@@ -211,7 +209,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_degree_kernel(const int* __restri
 // cursor[v] counts down from the segment's length: the slot order inside a segment is arbitrary, the sort removes it
 __global__ __launch_bounds__(MC_BLOCK) void mc_fill_kernel(const int* __restrict__ faces, int nv, int nf, const int* __restrict__ row_start, int* cursor,
                                                            int* __restrict__ nbr) {
-    const long long f = mc_id();
+    const long long f = gid();
     if (f >= nf) return;
     const int idx[3] = {faces[3 * f], faces[3 * f + 1], faces[3 * f + 2]};
     if (!mc::face_valid(idx[0], idx[1], idx[2], nv)) return;
@@ -260,7 +258,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_sort_kernel(int nv, const int* __
                                                            int heavy_capacity, u64* stats) {
     __shared__ int seg[MC_LIMIT * MC_BLOCK];                      // entry k of lane t at seg[k * MC_BLOCK + t]: no bank conflicts
     __shared__ unsigned sh[MC_BLOCK];
-    const long long v = mc_id();
+    const long long v = gid();
     const int t = threadIdx.x;
     McEdgeStats st = {0u, 0u, 0u};
     unsigned referenced = 0;
@@ -332,7 +330,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_sort_heavy_kernel(int nv, const i
 __global__ __launch_bounds__(MC_BLOCK) void mc_taubin_kernel(const float* __restrict__ src, float* __restrict__ dst, int nv, const int* __restrict__ row_start,
                                                              const int* __restrict__ row_len, const int* __restrict__ nbr, long long entries,
                                                              const unsigned char* __restrict__ pinned, double f) {
-    const long long v = mc_id();
+    const long long v = gid();
     if (v >= nv) return;
     const unsigned* sb = reinterpret_cast<const unsigned*>(src);
     unsigned* db = reinterpret_cast<unsigned*>(dst);
@@ -352,8 +350,6 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_taubin_kernel(const float* __rest
     }
 }
 
-static inline unsigned mc_blocks(long long n) { return (unsigned)(n > 0 ? cdiv(n, MC_BLOCK) : 1); }
-
 static int mc_sizes(const char* what, int nv, int nf) {
     RCMVS_REQUIRE(nv >= 0 && nf >= 0, "%s: %d vertices, %d faces (0 .. 2^31-1 each)", what, nv, nf);
     return 0;
@@ -369,10 +365,10 @@ extern "C" int rcmvs_mc_components_timed(const int* faces, int nv, int nf, int* 
     RCMVS_REQUIRE(counts && (nf == 0 || (faces && face_ok)) && (nv == 0 || (label && comp_faces)), "mc_components: null pointer");
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(mc_init_kernel, dim3(mc_blocks(nv)), dim3(MC_BLOCK), 0, st, e0, none, label, comp_faces, nv, counts);
-    hipLaunchKernelGGL(mc_hook_kernel, dim3(mc_blocks(nf)), dim3(MC_BLOCK), 0, st, faces, nv, nf, label, face_ok, counts);
-    hipLaunchKernelGGL(mc_flatten_kernel, dim3(mc_blocks(nv)), dim3(MC_BLOCK), 0, st, label, nv);
-    RCMVS_LAUNCH_TIMED(mc_face_count_kernel, dim3(mc_blocks(nf)), dim3(MC_BLOCK), 0, st, none, e1, faces, face_ok, nf, label, comp_faces);
+    RCMVS_LAUNCH_TIMED(mc_init_kernel, dim3(blocks(nv)), dim3(MC_BLOCK), 0, st, e0, none, label, comp_faces, nv, counts);
+    hipLaunchKernelGGL(mc_hook_kernel, dim3(blocks(nf)), dim3(MC_BLOCK), 0, st, faces, nv, nf, label, face_ok, counts);
+    hipLaunchKernelGGL(mc_flatten_kernel, dim3(blocks(nv)), dim3(MC_BLOCK), 0, st, label, nv);
+    RCMVS_LAUNCH_TIMED(mc_face_count_kernel, dim3(blocks(nf)), dim3(MC_BLOCK), 0, st, none, e1, faces, face_ok, nf, label, comp_faces);
     return launch_status("mc_components");
 }
 
@@ -388,10 +384,10 @@ extern "C" int rcmvs_mc_component_table_timed(const int* label, const int* comp_
     if (int rc = scan_work_check("mc_component_table", scan_work)) return rc;
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(zero_u64_kernel, dim3(1), dim3(MC_BLOCK), 0, st, e0, none, totals, 2);
-    hipLaunchKernelGGL(mc_root_flag_kernel, dim3(mc_blocks(nv)), dim3(MC_BLOCK), 0, st, label, comp_faces, nv, flags, totals);
+    RCMVS_LAUNCH_TIMED(zero_kernel<u64>, dim3(1), dim3(MC_BLOCK), 0, st, e0, none, totals, 2ll);
+    hipLaunchKernelGGL(mc_root_flag_kernel, dim3(blocks(nv)), dim3(MC_BLOCK), 0, st, label, comp_faces, nv, flags, totals);
     scan3<unsigned char>(flags, nv, rank, scan_work, totals, st, none, none);
-    RCMVS_LAUNCH_TIMED(mc_table_kernel, dim3(mc_blocks(nv)), dim3(MC_BLOCK), 0, st, none, e1, comp_faces, nv, flags, rank, table, capacity);
+    RCMVS_LAUNCH_TIMED(mc_table_kernel, dim3(blocks(nv)), dim3(MC_BLOCK), 0, st, none, e1, comp_faces, nv, flags, rank, table, capacity);
     return launch_status("mc_component_table");
 }
 
@@ -414,9 +410,9 @@ extern "C" int rcmvs_mc_select_timed(const int* faces, const unsigned char* face
     const int drop = drop_unreferenced != 0;
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(zero_u64_kernel, dim3(1), dim3(MC_BLOCK), 0, st, e0, none, totals, 3);
-    hipLaunchKernelGGL(mc_vert_init_kernel, dim3(mc_blocks(nv)), dim3(MC_BLOCK), 0, st, label, comp_faces, nv, sel, drop, vert_keep, totals);
-    hipLaunchKernelGGL(mc_face_keep_kernel, dim3(mc_blocks(nf)), dim3(MC_BLOCK), 0, st, faces, face_ok, label, comp_faces, nv, nf, sel, drop, face_keep,
+    RCMVS_LAUNCH_TIMED(zero_kernel<u64>, dim3(1), dim3(MC_BLOCK), 0, st, e0, none, totals, 3ll);
+    hipLaunchKernelGGL(mc_vert_init_kernel, dim3(blocks(nv)), dim3(MC_BLOCK), 0, st, label, comp_faces, nv, sel, drop, vert_keep, totals);
+    hipLaunchKernelGGL(mc_face_keep_kernel, dim3(blocks(nf)), dim3(MC_BLOCK), 0, st, faces, face_ok, label, comp_faces, nv, nf, sel, drop, face_keep,
                        vert_keep);
     scan3<unsigned char>(face_keep, nf, face_rank, scan_work, totals, st, none, none);
     scan3<unsigned char>(vert_keep, nv, vert_rank, scan_work, totals + 1, st, none, e1);
@@ -441,9 +437,9 @@ extern "C" int rcmvs_mc_gather_timed(const float* verts, const unsigned char* rg
     RCMVS_REQUIRE(!out_rgb || rgb, "mc_gather: null pointer (out_rgb needs rgb)");
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(mc_gather_verts_kernel, dim3(mc_blocks(nv)), dim3(MC_BLOCK), 0, st, e0, none, reinterpret_cast<const unsigned*>(verts), rgb, vert_keep,
+    RCMVS_LAUNCH_TIMED(mc_gather_verts_kernel, dim3(blocks(nv)), dim3(MC_BLOCK), 0, st, e0, none, reinterpret_cast<const unsigned*>(verts), rgb, vert_keep,
                        vert_rank, nv, nv_out, reinterpret_cast<unsigned*>(out_verts), out_rgb);
-    RCMVS_LAUNCH_TIMED(mc_gather_faces_kernel, dim3(mc_blocks(nf)), dim3(MC_BLOCK), 0, st, none, e1, faces, face_keep, face_rank, vert_rank, nv, nf, nf_out,
+    RCMVS_LAUNCH_TIMED(mc_gather_faces_kernel, dim3(blocks(nf)), dim3(MC_BLOCK), 0, st, none, e1, faces, face_keep, face_rank, vert_rank, nv, nf, nf_out,
                        out_faces);
     return launch_status("mc_gather");
 }
@@ -466,11 +462,11 @@ extern "C" int rcmvs_mc_adjacency_timed(const int* faces, int nv, int nf, int* r
     if (int rc = scan_work_check("mc_adjacency", scan_work)) return rc;
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(mc_zero_int_kernel, dim3(mc_blocks(nv)), dim3(MC_BLOCK), 0, st, e0, none, cursor, nv, stats);
-    hipLaunchKernelGGL(mc_degree_kernel, dim3(mc_blocks(nf)), dim3(MC_BLOCK), 0, st, faces, nv, nf, cursor);
+    RCMVS_LAUNCH_TIMED(mc_zero_int_kernel, dim3(blocks(nv)), dim3(MC_BLOCK), 0, st, e0, none, cursor, nv, stats);
+    hipLaunchKernelGGL(mc_degree_kernel, dim3(blocks(nf)), dim3(MC_BLOCK), 0, st, faces, nv, nf, cursor);
     scan3<int>(cursor, nv, row_start, scan_work, stats + 5, st, none, none);
-    hipLaunchKernelGGL(mc_fill_kernel, dim3(mc_blocks(nf)), dim3(MC_BLOCK), 0, st, faces, nv, nf, row_start, cursor, nbr);
-    hipLaunchKernelGGL(mc_sort_kernel, dim3(mc_blocks(nv)), dim3(MC_BLOCK), 0, st, nv, row_start, row_len, nbr, mult, on_boundary, heavy, heavy_capacity,
+    hipLaunchKernelGGL(mc_fill_kernel, dim3(blocks(nf)), dim3(MC_BLOCK), 0, st, faces, nv, nf, row_start, cursor, nbr);
+    hipLaunchKernelGGL(mc_sort_kernel, dim3(blocks(nv)), dim3(MC_BLOCK), 0, st, nv, row_start, row_len, nbr, mult, on_boundary, heavy, heavy_capacity,
                        stats);
     const int grid = heavy_capacity < MC_HEAVY_GRID ? heavy_capacity : MC_HEAVY_GRID;
     RCMVS_LAUNCH_TIMED(mc_sort_heavy_kernel, dim3(grid), dim3(MC_BLOCK), 0, st, none, e1, nv, row_start, row_len, nbr, mult, on_boundary, heavy,
@@ -494,7 +490,7 @@ extern "C" int rcmvs_mc_taubin_step_timed(const float* src, float* dst, int nv, 
         const uintptr_t a = reinterpret_cast<uintptr_t>(src), b = reinterpret_cast<uintptr_t>(dst), bytes = (uintptr_t)nv * 12;
         RCMVS_REQUIRE(a + bytes <= b || b + bytes <= a, "mc_taubin_step: src and dst overlap (a Jacobi step reads the old positions)");
     }
-    RCMVS_LAUNCH_TIMED(mc_taubin_kernel, dim3(mc_blocks(nv)), dim3(MC_BLOCK), 0, as_stream(stream), static_cast<hipEvent_t>(ev0), static_cast<hipEvent_t>(ev1),
+    RCMVS_LAUNCH_TIMED(mc_taubin_kernel, dim3(blocks(nv)), dim3(MC_BLOCK), 0, as_stream(stream), static_cast<hipEvent_t>(ev0), static_cast<hipEvent_t>(ev1),
                        src, dst, nv, row_start, row_len, nbr, entries, pinned, f);
     return launch_status("mc_taubin_step");
 }

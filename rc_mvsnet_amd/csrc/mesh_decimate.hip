@@ -23,7 +23,7 @@
 #include "common.h"
 #include "mesh_decimate.h"
 #include "mesh_decimate_math.h"
-#include "scan_sort.h"                                            // scan3, radix_hist_kernel, radix_scatter_kernel, zero_u64_kernel
+#include "scan_sort.h"                                            // gid, blocks, scan3, radix_sort, segments_kernel, zero_kernel
 #include "tsdf_mesh_cells.h"                                      // tm_block_sum (256 threads)
 
 #pragma clang fp contract(off)
@@ -43,30 +43,6 @@ struct MdLattice {
     long long g[3];
 };
 
-__device__ inline long long md_id() { return (long long)blockIdx.x * MD_BLOCK + threadIdx.x; }
-
-// `passes` stable passes from (*ka, *ia); on return *ka / *ia point at the buffers that hold the sorted pairs
-template <class K>
-static void md_sort(K** ka, int** ia, K** kb, int** ib, long long n, int passes, int* hist, int* hist_start, int* scan_work, hipStream_t st) {
-    if (n <= 0) return;
-    const long long nblk = cdiv(n, MD_BLOCK);
-    hipEvent_t none = nullptr;
-    for (int p = 0; p < passes; ++p) {
-        hipLaunchKernelGGL(radix_hist_kernel<K>, dim3((unsigned)nblk), dim3(MD_BLOCK), 0, st, *ka, n, 8 * p, nblk, hist);
-        scan3<int>(hist, 256 * nblk, hist_start, scan_work, nullptr, st, none, none);
-        hipLaunchKernelGGL(radix_scatter_kernel<K>, dim3((unsigned)nblk), dim3(MD_BLOCK), 0, st, *ka, *ia, n, 8 * p, nblk, hist_start, *kb, *ib);
-        K* tk = *ka; *ka = *kb; *kb = tk;
-        int* ti = *ia; *ia = *ib; *ib = ti;
-    }
-}
-
-static int md_passes(u64 largest_key) {
-    int bits = 0;
-    for (u64 top = largest_key; top; top >>= 1) ++bits;
-    const int passes = (bits + 7) / 8;
-    return passes < 1 ? 1 : passes;
-}
-
 // ---- bounds -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MD_BLOCK) void md_bounds_init_kernel(unsigned* __restrict__ bounds) {
     if (blockIdx.x == 0 && threadIdx.x < 8) bounds[threadIdx.x] = threadIdx.x < 3 ? 0xffffffffu : 0u;
@@ -75,7 +51,7 @@ __global__ __launch_bounds__(MD_BLOCK) void md_bounds_init_kernel(unsigned* __re
 __global__ __launch_bounds__(MD_BLOCK) void md_bounds_kernel(const float* __restrict__ verts, int nv, unsigned* bounds) {
     __shared__ unsigned sh[7][MD_BLOCK];
     unsigned lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u}, cnt = 0;
-    for (long long v = md_id(); v < nv; v += (long long)gridDim.x * MD_BLOCK) {
+    for (long long v = gid(); v < nv; v += (long long)gridDim.x * MD_BLOCK) {
         const float p[3] = {verts[3 * v], verts[3 * v + 1], verts[3 * v + 2]};
         if (!md::finite3(p[0], p[1], p[2])) continue;
         ++cnt;
@@ -126,7 +102,7 @@ __device__ inline bool md_cell(const float* __restrict__ verts, long long v, con
 __global__ __launch_bounds__(MD_BLOCK) void md_vertex_key_kernel(const float* __restrict__ verts, int nv, MdLattice L, u64 behind, u64* __restrict__ key,
                                                                  int* __restrict__ idx, u64* totals) {
     __shared__ unsigned sh[MD_BLOCK];
-    const long long v = md_id();
+    const long long v = gid();
     unsigned in = 0;
     if (v < nv) {
         long long k[3];
@@ -139,7 +115,7 @@ __global__ __launch_bounds__(MD_BLOCK) void md_vertex_key_kernel(const float* __
 }
 
 __global__ __launch_bounds__(MD_BLOCK) void md_head_kernel(const u64* __restrict__ key, int n, u64 behind, unsigned char* __restrict__ head) {
-    const long long i = md_id();
+    const long long i = gid();
     if (i < n) head[i] = (key[i] != behind && (i == 0 || key[i] != key[i - 1])) ? 1 : 0;
 }
 
@@ -147,7 +123,7 @@ __global__ __launch_bounds__(MD_BLOCK) void md_emit_kernel(const u64* __restrict
                                                            const int* __restrict__ head_rank, int n, u64 behind, const u64* __restrict__ totals,
                                                            int* __restrict__ cluster, int* __restrict__ order, int* __restrict__ cluster_start,
                                                            u64* __restrict__ cluster_key) {
-    const long long i = md_id();
+    const long long i = gid();
     if (i == 0) {
         const u64 m = totals[0];
         if (m <= (u64)n) cluster_start[m] = (int)totals[1];
@@ -167,7 +143,7 @@ __global__ __launch_bounds__(MD_BLOCK) void md_emit_kernel(const u64* __restrict
 constexpr int MD_EMPTY = -1;
 
 __global__ __launch_bounds__(MD_BLOCK) void md_table_init_kernel(int* __restrict__ table, long long capacity, u64* __restrict__ counts) {
-    for (long long i = md_id(); i < capacity; i += (long long)gridDim.x * MD_BLOCK) table[i] = MD_EMPTY;
+    for (long long i = gid(); i < capacity; i += (long long)gridDim.x * MD_BLOCK) table[i] = MD_EMPTY;
     if (blockIdx.x == 0 && threadIdx.x < 4) counts[threadIdx.x] = 0;
 }
 
@@ -181,7 +157,7 @@ __device__ inline u64 md_hash(const int* r) {
 __global__ __launch_bounds__(MD_BLOCK) void md_face_map_kernel(const int* __restrict__ faces, int nv, int nf, const int* __restrict__ cluster,
                                                                int* __restrict__ cface, unsigned char* __restrict__ face_class, u64* counts) {
     __shared__ unsigned sh[MD_BLOCK];
-    const long long f = md_id();
+    const long long f = gid();
     int cls = -1;
     if (f < nf) {
         const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
@@ -214,7 +190,7 @@ __device__ inline bool md_same_triple(const int* __restrict__ cface, long long g
 // slots in every order of execution; no thread waits: a failed CAS is another thread's success.
 __global__ __launch_bounds__(MD_BLOCK) void md_face_insert_kernel(const int* __restrict__ cface, const unsigned char* __restrict__ face_class, int nf,
                                                                   int* table, long long capacity) {
-    const long long f = md_id();
+    const long long f = gid();
     if (f >= nf || face_class[f] != RCMVS_MD_FACE_KEPT) return;
     int r[3];
     md::rotate_min_first(cface[3 * f], cface[3 * f + 1], cface[3 * f + 2], r);
@@ -232,7 +208,7 @@ __global__ __launch_bounds__(MD_BLOCK) void md_face_insert_kernel(const int* __r
 __global__ __launch_bounds__(MD_BLOCK) void md_face_resolve_kernel(const int* __restrict__ cface, unsigned char* __restrict__ face_class, int nf,
                                                                    const int* __restrict__ table, long long capacity, u64* counts) {
     __shared__ unsigned sh[MD_BLOCK];
-    const long long f = md_id();
+    const long long f = gid();
     unsigned dup = 0;
     if (f < nf && face_class[f] == RCMVS_MD_FACE_KEPT) {
         int r[3];
@@ -253,14 +229,9 @@ __global__ __launch_bounds__(MD_BLOCK) void md_face_resolve_kernel(const int* __
 }
 
 // ---- quadrics -----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(MD_BLOCK) void md_seg_zero_kernel(int* __restrict__ seg, long long n) {
-    const long long i = md_id();
-    if (i < n) seg[i] = 0;
-}
-
 __global__ __launch_bounds__(MD_BLOCK) void md_corner_key_kernel(const int* __restrict__ faces, int nv, long long n, const int* __restrict__ cluster, int m,
                                                                  unsigned* __restrict__ key, int* __restrict__ idx) {
-    const long long e = md_id();
+    const long long e = gid();
     if (e >= n) return;
     const long long f = e / 3;
     const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
@@ -274,15 +245,6 @@ __global__ __launch_bounds__(MD_BLOCK) void md_corner_key_kernel(const int* __re
     idx[e] = (int)e;
 }
 
-__global__ __launch_bounds__(MD_BLOCK) void md_seg_kernel(const unsigned* __restrict__ key, long long n, int m, int* __restrict__ seg) {
-    const long long i = md_id();
-    if (i >= n) return;
-    const unsigned k = key[i];
-    if (k >= (unsigned)m) return;
-    if (i == 0 || key[i - 1] != k) seg[2 * (size_t)k] = (int)i;
-    if (i == n - 1 || key[i + 1] != k) seg[2 * (size_t)k + 1] = (int)(i + 1);
-}
-
 __device__ inline void md_key_cell(u64 key, const MdLattice& L, long long* k) {
     const u64 gx = (u64)L.g[0], gy = (u64)L.g[1];
     k[0] = (long long)(key % gx);
@@ -293,7 +255,7 @@ __device__ inline void md_key_cell(u64 key, const MdLattice& L, long long* k) {
 __global__ __launch_bounds__(MD_BLOCK) void md_quadric_kernel(const float* __restrict__ verts, const int* __restrict__ faces, int nv, long long n,
                                                               const u64* __restrict__ cluster_key, int m, MdLattice L, const int* __restrict__ idx,
                                                               const int* __restrict__ seg, double* __restrict__ quad) {
-    const long long r = md_id();
+    const long long r = gid();
     if (r >= m) return;
     long long k[3];
     md_key_cell(cluster_key[r], L, k);
@@ -329,7 +291,7 @@ __global__ __launch_bounds__(MD_BLOCK) void md_place_kernel(const float* __restr
                                                             int placement, double reg, float* __restrict__ out_verts, unsigned char* __restrict__ out_rgb,
                                                             unsigned char* __restrict__ via_out, u64* counts) {
     __shared__ unsigned sh[MD_BLOCK];
-    const long long r = md_id();
+    const long long r = gid();
     int via = -1;
     if (r < m) {
         const long long s0 = cluster_start[r], s1 = cluster_start[r + 1];
@@ -391,21 +353,19 @@ __global__ __launch_bounds__(MD_BLOCK) void md_place_kernel(const float* __restr
 
 // ---- select -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MD_BLOCK) void md_vert_init_kernel(unsigned char* __restrict__ vert_keep, int m, int drop) {
-    const long long r = md_id();
+    const long long r = gid();
     if (r < m) vert_keep[r] = drop ? 0 : 1;
 }
 
 __global__ __launch_bounds__(MD_BLOCK) void md_face_keep_kernel(const int* __restrict__ cface, const unsigned char* __restrict__ face_class, int m, int nf,
                                                                 int drop, unsigned char* __restrict__ face_keep, unsigned char* vert_keep) {
-    const long long f = md_id();
+    const long long f = gid();
     if (f >= nf) return;
     const int a = cface[3 * f], b = cface[3 * f + 1], c = cface[3 * f + 2];
     const bool keep = face_class[f] == RCMVS_MD_FACE_KEPT && mc::face_valid(a, b, c, m);
     face_keep[f] = keep ? 1 : 0;
     if (keep && drop) { vert_keep[a] = 1; vert_keep[b] = 1; vert_keep[c] = 1; }      // every writer stores the same value
 }
-
-static inline unsigned md_blocks(long long n) { return (unsigned)(n > 0 ? cdiv(n, MD_BLOCK) : 1); }
 
 static int md_sizes(const char* what, int nv, int nf) {
     RCMVS_REQUIRE(nv >= 0 && nv <= RCMVS_MD_MAX_ELEMENTS, "%s: %d vertices (0 .. 2^31-256)", what, nv);
@@ -433,7 +393,7 @@ extern "C" int rcmvs_md_bounds_timed(const float* verts, int nv, unsigned* bound
     RCMVS_REQUIRE(bounds && (nv == 0 || verts), "md_bounds: null pointer");
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    const unsigned grid = md_blocks(nv) < (unsigned)MD_BOUNDS_GRID ? md_blocks(nv) : (unsigned)MD_BOUNDS_GRID;
+    const unsigned grid = blocks(nv) < (unsigned)MD_BOUNDS_GRID ? blocks(nv) : (unsigned)MD_BOUNDS_GRID;
     RCMVS_LAUNCH_TIMED(md_bounds_init_kernel, dim3(1), dim3(MD_BLOCK), 0, st, e0, none, bounds);
     RCMVS_LAUNCH_TIMED(md_bounds_kernel, dim3(grid), dim3(MD_BLOCK), 0, st, none, e1, verts, nv, bounds);
     return launch_status("md_bounds");
@@ -474,12 +434,12 @@ extern "C" int rcmvs_md_cluster_timed(const float* verts, int nv, const double* 
     const u64 behind = (u64)L.g[0] * (u64)L.g[1] * (u64)L.g[2];   // <= 2^63: the key of the vertices that are not clustered
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(zero_u64_kernel, dim3(1), dim3(MD_BLOCK), 0, st, e0, none, totals, 2);
-    hipLaunchKernelGGL(md_vertex_key_kernel, dim3(md_blocks(nv)), dim3(MD_BLOCK), 0, st, verts, nv, L, behind, key_a, idx_a, totals);
-    md_sort<u64>(&key_a, &idx_a, &key_b, &idx_b, nv, md_passes(behind), hist, hist_start, scan_work, st);
-    hipLaunchKernelGGL(md_head_kernel, dim3(md_blocks(nv)), dim3(MD_BLOCK), 0, st, key_a, nv, behind, head);
+    RCMVS_LAUNCH_TIMED(zero_kernel<u64>, dim3(1), dim3(MD_BLOCK), 0, st, e0, none, totals, 2ll);
+    hipLaunchKernelGGL(md_vertex_key_kernel, dim3(blocks(nv)), dim3(MD_BLOCK), 0, st, verts, nv, L, behind, key_a, idx_a, totals);
+    radix_sort<u64>(&key_a, &idx_a, &key_b, &idx_b, nv, radix_passes(behind), hist, hist_start, scan_work, st);
+    hipLaunchKernelGGL(md_head_kernel, dim3(blocks(nv)), dim3(MD_BLOCK), 0, st, key_a, nv, behind, head);
     scan3<unsigned char>(head, nv, head_rank, scan_work, totals, st, none, none);
-    RCMVS_LAUNCH_TIMED(md_emit_kernel, dim3(md_blocks(nv)), dim3(MD_BLOCK), 0, st, none, e1, key_a, idx_a, head, head_rank, nv, behind, totals, cluster, order,
+    RCMVS_LAUNCH_TIMED(md_emit_kernel, dim3(blocks(nv)), dim3(MD_BLOCK), 0, st, none, e1, key_a, idx_a, head, head_rank, nv, behind, totals, cluster, order,
                        cluster_start, cluster_key);
     return launch_status("md_cluster");
 }
@@ -499,11 +459,10 @@ extern "C" int rcmvs_md_classify_faces_timed(const int* faces, int nv, int nf, c
                   "md_classify_faces: table_capacity = %lld (a power of two above the %d faces)", table_capacity, nf);
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    const unsigned init_grid = md_blocks(table_capacity) < 65536u ? md_blocks(table_capacity) : 65536u;
-    RCMVS_LAUNCH_TIMED(md_table_init_kernel, dim3(init_grid), dim3(MD_BLOCK), 0, st, e0, none, table, table_capacity, counts);
-    hipLaunchKernelGGL(md_face_map_kernel, dim3(md_blocks(nf)), dim3(MD_BLOCK), 0, st, faces, nv, nf, cluster, cface, face_class, counts);
-    hipLaunchKernelGGL(md_face_insert_kernel, dim3(md_blocks(nf)), dim3(MD_BLOCK), 0, st, cface, face_class, nf, table, table_capacity);
-    RCMVS_LAUNCH_TIMED(md_face_resolve_kernel, dim3(md_blocks(nf)), dim3(MD_BLOCK), 0, st, none, e1, cface, face_class, nf, table, table_capacity, counts);
+    RCMVS_LAUNCH_TIMED(md_table_init_kernel, dim3(capped_blocks(table_capacity)), dim3(MD_BLOCK), 0, st, e0, none, table, table_capacity, counts);
+    hipLaunchKernelGGL(md_face_map_kernel, dim3(blocks(nf)), dim3(MD_BLOCK), 0, st, faces, nv, nf, cluster, cface, face_class, counts);
+    hipLaunchKernelGGL(md_face_insert_kernel, dim3(blocks(nf)), dim3(MD_BLOCK), 0, st, cface, face_class, nf, table, table_capacity);
+    RCMVS_LAUNCH_TIMED(md_face_resolve_kernel, dim3(blocks(nf)), dim3(MD_BLOCK), 0, st, none, e1, cface, face_class, nf, table, table_capacity, counts);
     return launch_status("md_classify_faces");
 }
 
@@ -525,11 +484,11 @@ extern "C" int rcmvs_md_quadrics_timed(const float* verts, const int* faces, int
     const long long n = 3ll * nf;
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(md_seg_zero_kernel, dim3(md_blocks(2ll * m)), dim3(MD_BLOCK), 0, st, e0, none, seg, 2ll * m);
-    hipLaunchKernelGGL(md_corner_key_kernel, dim3(md_blocks(n)), dim3(MD_BLOCK), 0, st, faces, nv, n, cluster, m, ckey_a, cidx_a);
-    md_sort<unsigned>(&ckey_a, &cidx_a, &ckey_b, &cidx_b, n, md_passes((u64)m), hist, hist_start, scan_work, st);
-    hipLaunchKernelGGL(md_seg_kernel, dim3(md_blocks(n)), dim3(MD_BLOCK), 0, st, ckey_a, n, m, seg);
-    RCMVS_LAUNCH_TIMED(md_quadric_kernel, dim3(md_blocks(m)), dim3(MD_BLOCK), 0, st, none, e1, verts, faces, nv, n, cluster_key, m, L, cidx_a, seg, quad);
+    RCMVS_LAUNCH_TIMED(zero_kernel<int>, dim3(blocks(2ll * m)), dim3(MD_BLOCK), 0, st, e0, none, seg, 2ll * m);
+    hipLaunchKernelGGL(md_corner_key_kernel, dim3(blocks(n)), dim3(MD_BLOCK), 0, st, faces, nv, n, cluster, m, ckey_a, cidx_a);
+    radix_sort<unsigned>(&ckey_a, &cidx_a, &ckey_b, &cidx_b, n, radix_passes((u64)m), hist, hist_start, scan_work, st);
+    hipLaunchKernelGGL(segments_kernel, dim3(blocks(n)), dim3(MD_BLOCK), 0, st, ckey_a, n, m, seg);
+    RCMVS_LAUNCH_TIMED(md_quadric_kernel, dim3(blocks(m)), dim3(MD_BLOCK), 0, st, none, e1, verts, faces, nv, n, cluster_key, m, L, cidx_a, seg, quad);
     return launch_status("md_quadrics");
 }
 
@@ -554,8 +513,8 @@ extern "C" int rcmvs_md_place_timed(const float* verts, const unsigned char* rgb
     RCMVS_REQUIRE(!out_rgb || rgb, "md_place: null pointer (out_rgb needs rgb)");
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(zero_u64_kernel, dim3(1), dim3(MD_BLOCK), 0, st, e0, none, counts, 3);
-    RCMVS_LAUNCH_TIMED(md_place_kernel, dim3(md_blocks(m)), dim3(MD_BLOCK), 0, st, none, e1, verts, rgb, nv, order, cluster_start, cluster_key, m, L, quad,
+    RCMVS_LAUNCH_TIMED(zero_kernel<u64>, dim3(1), dim3(MD_BLOCK), 0, st, e0, none, counts, 3ll);
+    RCMVS_LAUNCH_TIMED(md_place_kernel, dim3(blocks(m)), dim3(MD_BLOCK), 0, st, none, e1, verts, rgb, nv, order, cluster_start, cluster_key, m, L, quad,
                        placement, reg, out_verts, out_rgb, via, counts);
     return launch_status("md_place");
 }
@@ -576,8 +535,8 @@ extern "C" int rcmvs_md_select_timed(const int* cface, const unsigned char* face
     const int drop = drop_unreferenced != 0;
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(md_vert_init_kernel, dim3(md_blocks(m)), dim3(MD_BLOCK), 0, st, e0, none, vert_keep, m, drop);
-    hipLaunchKernelGGL(md_face_keep_kernel, dim3(md_blocks(nf)), dim3(MD_BLOCK), 0, st, cface, face_class, m, nf, drop, face_keep, vert_keep);
+    RCMVS_LAUNCH_TIMED(md_vert_init_kernel, dim3(blocks(m)), dim3(MD_BLOCK), 0, st, e0, none, vert_keep, m, drop);
+    hipLaunchKernelGGL(md_face_keep_kernel, dim3(blocks(nf)), dim3(MD_BLOCK), 0, st, cface, face_class, m, nf, drop, face_keep, vert_keep);
     scan3<unsigned char>(face_keep, nf, face_rank, scan_work, totals, st, none, none);
     scan3<unsigned char>(vert_keep, m, vert_rank, scan_work, totals + 1, st, none, e1);
     return launch_status("md_select");

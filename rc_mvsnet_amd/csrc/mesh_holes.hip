@@ -19,7 +19,7 @@
 #include "common.h"
 #include "mesh_holes.h"
 #include "mesh_holes_math.h"
-#include "scan_sort.h"                                            // scan3, zero_u64_kernel
+#include "scan_sort.h"                                            // gid, blocks, ranges_overlap, scan3, zero_kernel
 #include "tsdf_mesh_cells.h"                                      // tm_block_sum (256 threads)
 
 #pragma clang fp contract(off)
@@ -27,18 +27,16 @@
 namespace rcmvs {
 
 constexpr int MH_BLOCK = TM_BLOCK;
-static_assert(MH_BLOCK == SS_BLOCK, "zero_u64_kernel is launched with this family's block");
+static_assert(MH_BLOCK == SS_BLOCK, "gid, blocks and zero_kernel count in this family's block");
 static_assert(RCMVS_MH_SCAN_TILE == SS_TILE && RCMVS_MH_SCAN_WORK == SS_WORK, "mesh_holes.h describes scan_sort.h's work area");
 static_assert(mh::NONE == RCMVS_MH_NONE && mh::SIMPLE == RCMVS_MH_SIMPLE && mh::COMPLEX == RCMVS_MH_COMPLEX, "the flags of mesh_holes.h");
 
 using u64 = unsigned long long;
 
-__device__ inline long long mh_id() { return (long long)blockIdx.x * MH_BLOCK + threadIdx.x; }
-
 // ---- boundary -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MH_BLOCK) void mh_init_kernel(int nv, int* __restrict__ out_count, int* __restrict__ in_count, int* __restrict__ succ,
                                                            int* __restrict__ pred, u64* __restrict__ counts) {
-    const long long v = mh_id();
+    const long long v = gid();
     if (v < nv) { out_count[v] = 0; in_count[v] = 0; succ[v] = -1; pred[v] = -1; }
     if (v < 2) counts[v] = 0;
 }
@@ -63,7 +61,7 @@ __device__ inline int mh_multiplicity(int v, int w, const int* __restrict__ row_
 __global__ __launch_bounds__(MH_BLOCK) void mh_half_edge_kernel(const int* __restrict__ faces, int nv, long long corners, const int* __restrict__ row_start,
                                                                 const int* __restrict__ row_len, const int* __restrict__ nbr, const int* __restrict__ mult,
                                                                 long long entries, int* out_count, int* in_count, int* succ, int* pred) {
-    const long long e = mh_id();
+    const long long e = gid();
     if (e >= corners) return;
     const long long f = e / 3;
     const int k = (int)(e - 3 * f);
@@ -80,7 +78,7 @@ __global__ __launch_bounds__(MH_BLOCK) void mh_half_edge_kernel(const int* __res
 __global__ __launch_bounds__(MH_BLOCK) void mh_classify_kernel(int nv, const int* __restrict__ out_count, const int* __restrict__ in_count,
                                                                int* __restrict__ succ, int* __restrict__ pred, unsigned char* __restrict__ flags, u64* counts) {
     __shared__ unsigned sh[MH_BLOCK];
-    const long long v = mh_id();
+    const long long v = gid();
     unsigned leaving = 0, complex_here = 0;
     if (v < nv) {
         const int o = out_count[v], cls = mh::classify(o, in_count[v]);
@@ -114,7 +112,7 @@ __global__ __launch_bounds__(MH_BLOCK) void mh_leader_kernel(const int* __restri
                                                              int* __restrict__ loop_len, unsigned char* __restrict__ vert_count, int* __restrict__ face_count,
                                                              u64* totals) {
     __shared__ unsigned sh[MH_BLOCK];
-    const long long v = mh_id();
+    const long long v = gid();
     int L = 0;
     if (v < nv) {
         L = mh_loop_length(succ, pred, nv, (int)v, max_edges);
@@ -139,7 +137,7 @@ __global__ __launch_bounds__(MH_BLOCK) void mh_leader_kernel(const int* __restri
 // ---- emit ---------------------------------------------------------------------------------------------------------------------
 template <class T>
 __global__ __launch_bounds__(MH_BLOCK) void mh_copy_kernel(const T* __restrict__ src, long long n, T* __restrict__ dst) {
-    for (long long i = mh_id(); i < n; i += (long long)gridDim.x * MH_BLOCK) dst[i] = src[i];
+    for (long long i = gid(); i < n; i += (long long)gridDim.x * MH_BLOCK) dst[i] = src[i];
 }
 
 // One lane per leader.  The chain of succ is a chain of dependent loads whatever walks it, and the fp64 sum is in loop order, so
@@ -148,7 +146,7 @@ __global__ __launch_bounds__(MH_BLOCK) void mh_fan_kernel(const float* __restric
                                                           const int* __restrict__ succ, const int* __restrict__ loop_len, const int* __restrict__ vert_rank,
                                                           const int* __restrict__ face_rank, int nv_out, int nf_out, float* __restrict__ out_verts,
                                                           unsigned char* __restrict__ out_rgb, int* __restrict__ out_faces) {
-    const long long v = mh_id();
+    const long long v = gid();
     if (v >= nv) return;
     const int L = loop_len[v];
     if (L < 3 || L > RCMVS_MH_MAX_EDGES) return;
@@ -191,17 +189,9 @@ __global__ __launch_bounds__(MH_BLOCK) void mh_fan_kernel(const float* __restric
     }
 }
 
-static inline unsigned mh_blocks(long long n) { return (unsigned)(n > 0 ? cdiv(n, MH_BLOCK) : 1); }
-static inline unsigned mh_copy_blocks(long long n) { return mh_blocks(n) < 65536u ? mh_blocks(n) : 65536u; }
-
 static int mh_sizes(const char* what, int nv, int nf) {
     RCMVS_REQUIRE(nv >= 0 && nf >= 0, "%s: %d vertices, %d faces (0 .. 2^31-1 each)", what, nv, nf);
     return 0;
-}
-
-static bool mh_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return a && b && na && nb && x < y + nb && y < x + na;
 }
 
 }  // namespace rcmvs
@@ -217,10 +207,10 @@ extern "C" int rcmvs_mh_boundary_timed(const int* faces, int nv, int nf, const i
                   (entries == 0 || (nbr && mult)), "mh_boundary: null pointer");
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(mh_init_kernel, dim3(mh_blocks(nv)), dim3(MH_BLOCK), 0, st, e0, none, nv, out_count, in_count, succ, pred, counts);
-    hipLaunchKernelGGL(mh_half_edge_kernel, dim3(mh_blocks(3ll * nf)), dim3(MH_BLOCK), 0, st, faces, nv, 3ll * nf, row_start, row_len, nbr, mult, entries,
+    RCMVS_LAUNCH_TIMED(mh_init_kernel, dim3(blocks(nv)), dim3(MH_BLOCK), 0, st, e0, none, nv, out_count, in_count, succ, pred, counts);
+    hipLaunchKernelGGL(mh_half_edge_kernel, dim3(blocks(3ll * nf)), dim3(MH_BLOCK), 0, st, faces, nv, 3ll * nf, row_start, row_len, nbr, mult, entries,
                        out_count, in_count, succ, pred);
-    RCMVS_LAUNCH_TIMED(mh_classify_kernel, dim3(mh_blocks(nv)), dim3(MH_BLOCK), 0, st, none, e1, nv, out_count, in_count, succ, pred, flags, counts);
+    RCMVS_LAUNCH_TIMED(mh_classify_kernel, dim3(blocks(nv)), dim3(MH_BLOCK), 0, st, none, e1, nv, out_count, in_count, succ, pred, flags, counts);
     return launch_status("mh_boundary");
 }
 
@@ -239,8 +229,8 @@ extern "C" int rcmvs_mh_leaders_timed(const int* succ, const int* pred, int nv, 
     if (int rc = scan_work_check("mh_leaders", scan_work)) return rc;
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(zero_u64_kernel, dim3(1), dim3(MH_BLOCK), 0, st, e0, none, totals, 5);
-    hipLaunchKernelGGL(mh_leader_kernel, dim3(mh_blocks(nv)), dim3(MH_BLOCK), 0, st, succ, pred, nv, max_edges, loop_len, vert_count, face_count, totals);
+    RCMVS_LAUNCH_TIMED(zero_kernel<u64>, dim3(1), dim3(MH_BLOCK), 0, st, e0, none, totals, 5ll);
+    hipLaunchKernelGGL(mh_leader_kernel, dim3(blocks(nv)), dim3(MH_BLOCK), 0, st, succ, pred, nv, max_edges, loop_len, vert_count, face_count, totals);
     scan3<unsigned char>(vert_count, nv, vert_rank, scan_work, totals, st, none, none);
     scan3<int>(face_count, nv, face_rank, scan_work, totals + 1, st, none, e1);
     return launch_status("mh_leaders");
@@ -260,16 +250,16 @@ extern "C" int rcmvs_mh_emit_timed(const float* verts, const unsigned char* rgb,
     RCMVS_REQUIRE((nv == 0 || (verts && succ && loop_len && vert_rank && face_rank)) && (nf == 0 || faces) && (nv_out == 0 || out_verts) &&
                   (nf_out == 0 || out_faces), "mh_emit: null pointer");
     RCMVS_REQUIRE(!out_rgb || rgb || nv == 0, "mh_emit: null pointer (out_rgb needs rgb)");
-    RCMVS_REQUIRE(!mh_overlap(verts, (size_t)nv * 12, out_verts, (size_t)nv_out * 12) && !mh_overlap(faces, (size_t)nf * 12, out_faces, (size_t)nf_out * 12) &&
-                  !mh_overlap(rgb, (size_t)nv * 3, out_rgb, (size_t)nv_out * 3), "mh_emit: an output overlaps its input");
+    RCMVS_REQUIRE(!ranges_overlap(verts, (size_t)nv * 12, out_verts, (size_t)nv_out * 12) && !ranges_overlap(faces, (size_t)nf * 12, out_faces, (size_t)nf_out * 12) &&
+                  !ranges_overlap(rgb, (size_t)nv * 3, out_rgb, (size_t)nv_out * 3), "mh_emit: an output overlaps its input");
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
     const long long wv = 3ll * nv, wf = 3ll * nf;
-    RCMVS_LAUNCH_TIMED(mh_copy_kernel<unsigned>, dim3(mh_copy_blocks(wv)), dim3(MH_BLOCK), 0, st, e0, none, reinterpret_cast<const unsigned*>(verts), wv,
+    RCMVS_LAUNCH_TIMED(mh_copy_kernel<unsigned>, dim3(capped_blocks(wv)), dim3(MH_BLOCK), 0, st, e0, none, reinterpret_cast<const unsigned*>(verts), wv,
                        reinterpret_cast<unsigned*>(out_verts));
-    hipLaunchKernelGGL(mh_copy_kernel<int>, dim3(mh_copy_blocks(wf)), dim3(MH_BLOCK), 0, st, faces, wf, out_faces);
-    if (out_rgb) hipLaunchKernelGGL(mh_copy_kernel<unsigned char>, dim3(mh_copy_blocks(wv)), dim3(MH_BLOCK), 0, st, rgb, wv, out_rgb);
-    RCMVS_LAUNCH_TIMED(mh_fan_kernel, dim3(mh_blocks(nv)), dim3(MH_BLOCK), 0, st, none, e1, verts, rgb, nv, nf, succ, loop_len, vert_rank, face_rank, nv_out,
+    hipLaunchKernelGGL(mh_copy_kernel<int>, dim3(capped_blocks(wf)), dim3(MH_BLOCK), 0, st, faces, wf, out_faces);
+    if (out_rgb) hipLaunchKernelGGL(mh_copy_kernel<unsigned char>, dim3(capped_blocks(wv)), dim3(MH_BLOCK), 0, st, rgb, wv, out_rgb);
+    RCMVS_LAUNCH_TIMED(mh_fan_kernel, dim3(blocks(nv)), dim3(MH_BLOCK), 0, st, none, e1, verts, rgb, nv, nf, succ, loop_len, vert_rank, face_rank, nv_out,
                        nf_out, out_verts, out_rgb, out_faces);
     return launch_status("mh_emit");
 }

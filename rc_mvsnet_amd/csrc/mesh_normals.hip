@@ -19,7 +19,7 @@
 #include "common.h"
 #include "mesh_normals.h"
 #include "mesh_normals_math.h"
-#include "scan_sort.h"                                            // scan3, radix_hist_kernel, radix_scatter_kernel, zero_u64_kernel
+#include "scan_sort.h"                                            // gid, blocks, the overlap checks, radix_sort, segments_kernel, zero_kernel
 #include "tsdf_mesh_cells.h"                                      // tm_block_sum (256 threads)
 
 #pragma clang fp contract(off)
@@ -31,8 +31,6 @@ static_assert(MN_BLOCK == RCMVS_MN_SORT_BLOCK && MN_BLOCK == SS_BLOCK, "a sort b
 static_assert(mn::AREA == RCMVS_MN_WEIGHT_AREA && mn::SPHERE == RCMVS_MN_WEIGHT_SPHERE && mn::CANCELLED < RCMVS_MN_STATS, "the constants of mesh_normals.h");
 
 using u64 = unsigned long long;
-
-__device__ inline long long mn_id() { return (long long)blockIdx.x * MN_BLOCK + threadIdx.x; }
 
 // the three vertices of a valid face into registers
 __device__ inline void mn_load(const float* __restrict__ verts, int i, float* p) {
@@ -51,7 +49,7 @@ __device__ inline void mn_count(int what, int first, int count, u64* stats, unsi
 
 // ---- face normals -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MN_BLOCK) void mn_face_kernel(const float* __restrict__ verts, const int* __restrict__ faces, int nv, int nf, float* __restrict__ out) {
-    const long long f = mn_id();
+    const long long f = gid();
     if (f >= nf) return;
     const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
     float n[3] = {0.0f, 0.0f, 0.0f};
@@ -71,7 +69,7 @@ __global__ __launch_bounds__(MN_BLOCK) void mn_face_kernel(const float* __restri
 __global__ __launch_bounds__(MN_BLOCK) void mn_key_kernel(const float* __restrict__ verts, const int* __restrict__ faces, int nv, int nf,
                                                           unsigned* __restrict__ key, int* __restrict__ idx, u64* stats) {
     __shared__ unsigned sh[MN_BLOCK];
-    const long long f = mn_id();
+    const long long f = gid();
     int what = -1;
     if (f < nf) {
         const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
@@ -100,26 +98,12 @@ __global__ __launch_bounds__(MN_BLOCK) void mn_key_kernel(const float* __restric
     mn_count(what, mn::INVALID, 3, stats, sh);
 }
 
-__global__ __launch_bounds__(MN_BLOCK) void mn_seg_zero_kernel(int* __restrict__ seg, long long n) {
-    const long long i = mn_id();
-    if (i < n) seg[i] = 0;
-}
-
-__global__ __launch_bounds__(MN_BLOCK) void mn_seg_kernel(const unsigned* __restrict__ key, long long n, int nv, int* __restrict__ seg) {
-    const long long i = mn_id();
-    if (i >= n) return;
-    const unsigned k = key[i];
-    if (k >= (unsigned)nv) return;
-    if (i == 0 || key[i - 1] != k) seg[2 * (size_t)k] = (int)i;
-    if (i == n - 1 || key[i + 1] != k) seg[2 * (size_t)k + 1] = (int)(i + 1);
-}
-
 // ---- accumulation -------------------------------------------------------------------------------------------------------------------
 // seg and idx are this call's own work; they are still tested before they are used as addresses.
 __global__ __launch_bounds__(MN_BLOCK) void mn_accumulate_kernel(const float* __restrict__ verts, const int* __restrict__ faces, int nv, long long n, int weight,
                                                                  const int* __restrict__ idx, const int* __restrict__ seg, float* __restrict__ normals, u64* stats) {
     __shared__ unsigned sh[MN_BLOCK];
-    const long long v = mn_id();
+    const long long v = gid();
     int what = -1;
     unsigned skipped = 0;
     if (v < nv) {
@@ -174,7 +158,7 @@ __global__ __launch_bounds__(MN_BLOCK) void mn_accumulate_kernel(const float* __
 __global__ __launch_bounds__(MN_BLOCK) void mn_shade_kernel(const float* __restrict__ verts, const int* __restrict__ faces, const float* __restrict__ normals, int nv,
                                                             int nf, mr::Cam cam, double near_z, int H, int W, const int* __restrict__ face_image, int background,
                                                             float* __restrict__ normal_map, unsigned char* __restrict__ smooth, unsigned char* __restrict__ normal_rgb) {
-    const long long p = mn_id(), pixels = (long long)H * W;
+    const long long p = gid(), pixels = (long long)H * W;
     if (p >= pixels) return;
     mn::Pixel px;
     px.normal[0] = px.normal[1] = px.normal[2] = 0.0f;
@@ -214,24 +198,10 @@ __global__ __launch_bounds__(MN_BLOCK) void mn_shade_kernel(const float* __restr
     normal_rgb[3 * p + 2] = px.rgb[2];
 }
 
-static inline unsigned mn_blocks(long long n) { return (unsigned)(n > 0 ? cdiv(n, MN_BLOCK) : 1); }
-
-static bool mn_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
-
 static int mn_sizes(const char* what, int nv, int nf) {
     RCMVS_REQUIRE(nv >= 0, "%s: nv = %d vertices (0 .. 2^31-1)", what, nv);
     RCMVS_REQUIRE(nf >= 0 && 3ll * nf <= RCMVS_MN_MAX_CORNERS, "%s: nf = %d faces (0 .. (2^31-256) / 3)", what, nf);
     return 0;
-}
-
-static int mn_passes(u64 largest_key) {
-    int bits = 0;
-    for (u64 top = largest_key; top; top >>= 1) ++bits;
-    const int passes = (bits + 7) / 8;
-    return passes < 1 ? 1 : passes;
 }
 
 }  // namespace rcmvs
@@ -245,11 +215,11 @@ extern "C" int rcmvs_mn_face_normals_timed(const float* verts, const int* faces,
     RCMVS_REQUIRE(nf == 0 || faces, "mn_face_normals: null pointer (faces)");
     RCMVS_REQUIRE(nf == 0 || face_normals, "mn_face_normals: null pointer (face_normals)");
     RCMVS_REQUIRE((reinterpret_cast<uintptr_t>(face_normals) & 3) == 0, "mn_face_normals: face_normals must be 4-byte aligned");
-    RCMVS_REQUIRE(!mn_overlap(face_normals, (size_t)nf * 12, verts, (size_t)nv * 12) && !mn_overlap(face_normals, (size_t)nf * 12, faces, (size_t)nf * 12),
+    RCMVS_REQUIRE(!ranges_overlap(face_normals, (size_t)nf * 12, verts, (size_t)nv * 12) && !ranges_overlap(face_normals, (size_t)nf * 12, faces, (size_t)nf * 12),
                   "mn_face_normals: face_normals overlaps an input");
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1);
-    RCMVS_LAUNCH_TIMED(mn_face_kernel, dim3(mn_blocks(nf)), dim3(MN_BLOCK), 0, st, e0, e1, verts, faces, nv, nf, face_normals);
+    RCMVS_LAUNCH_TIMED(mn_face_kernel, dim3(blocks(nf)), dim3(MN_BLOCK), 0, st, e0, e1, verts, faces, nv, nf, face_normals);
     return launch_status("mn_face_normals");
 }
 
@@ -275,29 +245,17 @@ extern "C" int rcmvs_mn_vertex_normals_timed(const float* verts, const int* face
         const void* ptr[] = {key_a, idx_a, key_b, idx_b, hist, hist_start, seg, normals, stats, verts, faces};
         const size_t len[] = {(size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)table * 4, (size_t)(table + 1) * 4, (size_t)nv * 8,
                               (size_t)nv * 12, (size_t)RCMVS_MN_STATS * 8, (size_t)nv * 12, (size_t)nf * 12};
-        for (int i = 0; i < 9; ++i)                                   // every output and work buffer against everything after it
-            for (int j = i + 1; j < 11; ++j)
-                RCMVS_REQUIRE(!mn_overlap(ptr[i], len[i], ptr[j], len[j]), "mn_vertex_normals: an output or work buffer overlaps another buffer");
+        if (int rc = buffers_overlap("mn_vertex_normals", ptr, len, 9, 11)) return rc;
     }
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
     const bool all = phase == RCMVS_MN_PHASE_ALL, inc = phase == RCMVS_MN_PHASE_INCIDENCE, acc = phase == RCMVS_MN_PHASE_ACCUMULATE;
-    RCMVS_LAUNCH_TIMED(zero_u64_kernel, dim3(1), dim3(MN_BLOCK), 0, st, (all || inc) ? e0 : none, none, stats, RCMVS_MN_STATS);
-    hipLaunchKernelGGL(mn_seg_zero_kernel, dim3(mn_blocks(2ll * nv)), dim3(MN_BLOCK), 0, st, seg, 2ll * nv);
-    hipLaunchKernelGGL(mn_key_kernel, dim3(mn_blocks(nf)), dim3(MN_BLOCK), 0, st, verts, faces, nv, nf, key_a, idx_a, stats);
-    if (n > 0) {
-        const long long nblk = cdiv(n, MN_BLOCK);
-        const int passes = mn_passes((u64)nv);                        // the sentinel nv is the largest key
-        for (int p = 0; p < passes; ++p) {
-            hipLaunchKernelGGL(radix_hist_kernel<unsigned>, dim3((unsigned)nblk), dim3(MN_BLOCK), 0, st, key_a, n, 8 * p, nblk, hist);
-            scan3<int>(hist, 256 * nblk, hist_start, scan_work, nullptr, st, none, none);
-            hipLaunchKernelGGL(radix_scatter_kernel<unsigned>, dim3((unsigned)nblk), dim3(MN_BLOCK), 0, st, key_a, idx_a, n, 8 * p, nblk, hist_start, key_b, idx_b);
-            unsigned* tk = key_a; key_a = key_b; key_b = tk;
-            int* ti = idx_a; idx_a = idx_b; idx_b = ti;
-        }
-    }
-    RCMVS_LAUNCH_TIMED(mn_seg_kernel, dim3(mn_blocks(n)), dim3(MN_BLOCK), 0, st, none, inc ? e1 : none, key_a, n, nv, seg);
-    RCMVS_LAUNCH_TIMED(mn_accumulate_kernel, dim3(mn_blocks(nv)), dim3(MN_BLOCK), 0, st, acc ? e0 : none, (all || acc) ? e1 : none, verts, faces, nv, n, weight,
+    RCMVS_LAUNCH_TIMED(zero_kernel<u64>, dim3(1), dim3(MN_BLOCK), 0, st, (all || inc) ? e0 : none, none, stats, (long long)RCMVS_MN_STATS);
+    hipLaunchKernelGGL(zero_kernel<int>, dim3(blocks(2ll * nv)), dim3(MN_BLOCK), 0, st, seg, 2ll * nv);
+    hipLaunchKernelGGL(mn_key_kernel, dim3(blocks(nf)), dim3(MN_BLOCK), 0, st, verts, faces, nv, nf, key_a, idx_a, stats);
+    radix_sort<unsigned>(&key_a, &idx_a, &key_b, &idx_b, n, radix_passes((u64)nv), hist, hist_start, scan_work, st);      // the sentinel nv is the largest key
+    RCMVS_LAUNCH_TIMED(segments_kernel, dim3(blocks(n)), dim3(MN_BLOCK), 0, st, none, inc ? e1 : none, key_a, n, nv, seg);
+    RCMVS_LAUNCH_TIMED(mn_accumulate_kernel, dim3(blocks(nv)), dim3(MN_BLOCK), 0, st, acc ? e0 : none, (all || acc) ? e1 : none, verts, faces, nv, n, weight,
                        idx_a, seg, normals, stats);
     return launch_status("mn_vertex_normals");
 }
@@ -329,14 +287,14 @@ extern "C" int rcmvs_mn_shade_timed(const float* verts, const int* faces, const 
         const size_t len[] = {all * 12, all, all * 3, (size_t)nv * 12, (size_t)nf * 12, (size_t)nv * 12, all * 4};
         for (int i = 0; i < 3; ++i)
             for (int j = i + 1; j < 7; ++j)
-                RCMVS_REQUIRE(!mn_overlap(ptr[i], len[i], ptr[j], len[j]), "mn_shade: an output overlaps another buffer");
+                RCMVS_REQUIRE(!ranges_overlap(ptr[i], len[i], ptr[j], len[j]), "mn_shade: an output overlaps another buffer");
     }
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
     for (int v = 0; v < n; ++v) {
         mr::Cam cam;
         for (int k = 0; k < 16; ++k) cam.c[k] = cams_host[16 * (size_t)v + k];
-        RCMVS_LAUNCH_TIMED(mn_shade_kernel, dim3(mn_blocks((long long)pixels)), dim3(MN_BLOCK), 0, st, v == 0 ? e0 : none, v == n - 1 ? e1 : none, verts, faces, normals,
+        RCMVS_LAUNCH_TIMED(mn_shade_kernel, dim3(blocks((long long)pixels)), dim3(MN_BLOCK), 0, st, v == 0 ? e0 : none, v == n - 1 ? e1 : none, verts, faces, normals,
                            nv, nf, cam, near_z, H, W, face_image + (size_t)v * pixels, background, normal_map + (size_t)v * pixels * 3, smooth + (size_t)v * pixels,
                            normal_rgb + (size_t)v * pixels * 3);
     }

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "mesh_render.h"
 #include "mesh_render_math.h"
+#include "scan_sort.h"                                            // gid, blocks, the overlap checks
 #include "tsdf_mesh_cells.h"                                      // tm_block_sum (256 threads)
 
 #pragma clang fp contract(off)
@@ -36,12 +37,11 @@ static_assert(sizeof(mr::Proj) == RCMVS_MR_PROJ_BYTES, "proj_work holds one mr::
 static_assert(mr::SMALL_SIDE == RCMVS_MR_SMALL_SIDE && mr::MAX_SIDE == RCMVS_MR_MAX_SIDE && mr::NONE == RCMVS_MR_CULL_NONE && mr::BACK == RCMVS_MR_CULL_BACK,
               "the constants of mesh_render.h");
 static_assert(mr::COVERED < RCMVS_MR_STATS && RCMVS_MR_TRACE == 10 && RCMVS_MR_TABLE == 8, "the tables of mesh_render.h");
-
-__device__ inline long long mr_id() { return (long long)blockIdx.x * MR_BLOCK + threadIdx.x; }
+static_assert(MR_BLOCK == SS_BLOCK, "gid and blocks count in this family's block");
 
 // ---- clear, project -------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MR_BLOCK) void mr_clear_kernel(u64* __restrict__ keys, long long pixels, u64* __restrict__ stats, int* __restrict__ list) {
-    for (long long i = mr_id(); i < pixels; i += (long long)gridDim.x * MR_BLOCK) keys[i] = mr::EMPTY;
+    for (long long i = gid(); i < pixels; i += (long long)gridDim.x * MR_BLOCK) keys[i] = mr::EMPTY;
     if (blockIdx.x == 0) {
         if ((int)threadIdx.x < RCMVS_MR_STATS) stats[threadIdx.x] = 0;
         if (threadIdx.x == 0) list[0] = 0;
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(MR_BLOCK) void mr_clear_kernel(u64* __restrict__ ke
 }
 
 __global__ __launch_bounds__(MR_BLOCK) void mr_project_kernel(const float* __restrict__ verts, int nv, mr::Cam cam, double near_z, mr::Proj* __restrict__ proj) {
-    const long long v = mr_id();
+    const long long v = gid();
     if (v >= nv) return;
     proj[v] = mr::project(cam.c, near_z, mr::camera(cam.c, verts[3 * v], verts[3 * v + 1], verts[3 * v + 2]));
 }
@@ -76,7 +76,7 @@ __device__ inline int mr_histogram_bin(int side) {
 __global__ __launch_bounds__(MR_BLOCK) void mr_small_kernel(const int* __restrict__ faces, int nv, int nf, const mr::Proj* __restrict__ proj, int H, int W, int cull,
                                                             u64* keys, int* list, u64* stats, u64* trace) {
     __shared__ unsigned sh[MR_BLOCK];
-    const long long f = mr_id();
+    const long long f = gid();
     int what = -1;                                                // the counter this face adds to
     unsigned inside = 0, issued = 0, large = 0;
     if (f < nf) {
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(MR_BLOCK) void mr_resolve_kernel(const float* __res
                                                               float* __restrict__ depth, int* __restrict__ face, unsigned char* __restrict__ out_rgb,
                                                               unsigned char* __restrict__ shade, u64* stats) {
     __shared__ unsigned sh[MR_BLOCK];
-    const long long p = mr_id(), pixels = (long long)H * W;
+    const long long p = gid(), pixels = (long long)H * W;
     unsigned covered = 0;
     if (p < pixels) {
         const u64 k = keys[p];
@@ -236,7 +236,7 @@ __device__ inline double mr_block_sum_f64(double v, double* sh) {
 }
 
 __global__ __launch_bounds__(MR_BLOCK) void mr_compare_clear_kernel(u64* __restrict__ table, long long cells) {
-    const long long i = mr_id();
+    const long long i = gid();
     if (i < cells) table[i] = 0;
 }
 
@@ -281,14 +281,6 @@ __global__ __launch_bounds__(MR_BLOCK) void mr_compare_sum_kernel(const double* 
     if (threadIdx.x == 0) table[view * RCMVS_MR_TABLE + 6] = __builtin_bit_cast(u64, total);
 }
 
-static inline unsigned mr_blocks(long long n) { return (unsigned)(n > 0 ? cdiv(n, MR_BLOCK) : 1); }
-static inline unsigned mr_capped_blocks(long long n) { return mr_blocks(n) < 65536u ? mr_blocks(n) : 65536u; }
-
-static bool mr_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
-
 static int mr_size(const char* what, int n, int H, int W) {
     RCMVS_REQUIRE(n >= 1, "%s: n = %d views (at least 1)", what, n);
     RCMVS_REQUIRE(H >= 1 && H <= RCMVS_MR_MAX_SIDE, "%s: H = %d (1 .. %d)", what, H, RCMVS_MR_MAX_SIDE);
@@ -318,9 +310,7 @@ extern "C" int rcmvs_mr_render_timed(const float* verts, const unsigned char* rg
         const void* ptr[] = {proj_work, list_work, keys, depth, face, out_rgb, shade, stats, trace, verts, rgb, faces};
         const size_t len[] = {(size_t)nv * RCMVS_MR_PROJ_BYTES, ((size_t)nf + 1) * 4, all * 8, all * 4, all * 4, all * 3, all, (size_t)n * RCMVS_MR_STATS * 8,
                               (size_t)RCMVS_MR_TRACE * 8, (size_t)nv * 12, (size_t)nv * 3, (size_t)nf * 12};
-        for (int i = 0; i < 9; ++i)                                   // every output and work buffer against everything after it
-            for (int j = i + 1; j < 12; ++j)
-                RCMVS_REQUIRE(!mr_overlap(ptr[i], len[i], ptr[j], len[j]), "mr_render: an output or work buffer overlaps another buffer");
+        if (int rc = buffers_overlap("mr_render", ptr, len, 9, 12)) return rc;
     }
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
@@ -343,14 +333,14 @@ extern "C" int rcmvs_mr_render_timed(const float* verts, const unsigned char* rg
         u64* keys_v = keys + (size_t)v * pixels;
         u64* stats_v = stats + (size_t)v * RCMVS_MR_STATS;
         // project before clear in the stream, so that the phase "small" (clear + small) is one run of launches
-        RCMVS_LAUNCH_TIMED(mr_project_kernel, dim3(mr_blocks(nv)), dim3(MR_BLOCK), 0, st, first(1), stop(1), verts, nv, cam, near_z, proj);
-        RCMVS_LAUNCH_TIMED(mr_clear_kernel, dim3(mr_capped_blocks((long long)pixels)), dim3(MR_BLOCK), 0, st, first(0), stop(0), keys_v, (long long)pixels, stats_v,
+        RCMVS_LAUNCH_TIMED(mr_project_kernel, dim3(blocks(nv)), dim3(MR_BLOCK), 0, st, first(1), stop(1), verts, nv, cam, near_z, proj);
+        RCMVS_LAUNCH_TIMED(mr_clear_kernel, dim3(capped_blocks((long long)pixels)), dim3(MR_BLOCK), 0, st, first(0), stop(0), keys_v, (long long)pixels, stats_v,
                            list_work);
-        RCMVS_LAUNCH_TIMED(mr_small_kernel, dim3(mr_blocks(nf)), dim3(MR_BLOCK), 0, st, first(2), stop(2), faces, nv, nf, proj, H, W, cull, keys_v, list_work, stats_v,
+        RCMVS_LAUNCH_TIMED(mr_small_kernel, dim3(blocks(nf)), dim3(MR_BLOCK), 0, st, first(2), stop(2), faces, nv, nf, proj, H, W, cull, keys_v, list_work, stats_v,
                            trace);
         RCMVS_LAUNCH_TIMED(mr_large_kernel, dim3(nf < MR_LARGE_GRID ? (nf > 0 ? nf : 1) : MR_LARGE_GRID, RCMVS_MR_LARGE_SLICES), dim3(MR_BLOCK), 0, st, first(3),
                            stop(3), faces, nv, nf, proj, H, W, keys_v, list_work, trace);
-        RCMVS_LAUNCH_TIMED(mr_resolve_kernel, dim3(mr_blocks((long long)pixels)), dim3(MR_BLOCK), 0, st, first(4), stop(4), verts, rgb, faces, nv, nf, cam, near_z, H, W,
+        RCMVS_LAUNCH_TIMED(mr_resolve_kernel, dim3(blocks((long long)pixels)), dim3(MR_BLOCK), 0, st, first(4), stop(4), verts, rgb, faces, nv, nf, cam, near_z, H, W,
                            keys_v, background, depth + (size_t)v * pixels, face + (size_t)v * pixels, out_rgb + (size_t)v * pixels * 3, shade + (size_t)v * pixels,
                            stats_v);
     }
@@ -377,14 +367,14 @@ extern "C" int rcmvs_mr_compare_timed(const float* rendered, const float* depth,
     }
     const long long pixels = (long long)H * W;
     const int tiles = (int)cdiv(pixels, RCMVS_MR_CMP_TILE);
-    RCMVS_REQUIRE(!mr_overlap(table, (size_t)n * RCMVS_MR_TABLE * 8, partial_work, (size_t)n * tiles * 8) &&
-                  !mr_overlap(table, (size_t)n * RCMVS_MR_TABLE * 8, rendered, (size_t)n * pixels * 4) &&
-                  !mr_overlap(table, (size_t)n * RCMVS_MR_TABLE * 8, depth, (size_t)n * pixels * 4) &&
-                  !mr_overlap(partial_work, (size_t)n * tiles * 8, rendered, (size_t)n * pixels * 4) &&
-                  !mr_overlap(partial_work, (size_t)n * tiles * 8, depth, (size_t)n * pixels * 4), "mr_compare: an output or work buffer overlaps another buffer");
+    RCMVS_REQUIRE(!ranges_overlap(table, (size_t)n * RCMVS_MR_TABLE * 8, partial_work, (size_t)n * tiles * 8) &&
+                  !ranges_overlap(table, (size_t)n * RCMVS_MR_TABLE * 8, rendered, (size_t)n * pixels * 4) &&
+                  !ranges_overlap(table, (size_t)n * RCMVS_MR_TABLE * 8, depth, (size_t)n * pixels * 4) &&
+                  !ranges_overlap(partial_work, (size_t)n * tiles * 8, rendered, (size_t)n * pixels * 4) &&
+                  !ranges_overlap(partial_work, (size_t)n * tiles * 8, depth, (size_t)n * pixels * 4), "mr_compare: an output or work buffer overlaps another buffer");
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(mr_compare_clear_kernel, dim3(mr_blocks((long long)n * RCMVS_MR_TABLE)), dim3(MR_BLOCK), 0, st, e0, none, table, (long long)n * RCMVS_MR_TABLE);
+    RCMVS_LAUNCH_TIMED(mr_compare_clear_kernel, dim3(blocks((long long)n * RCMVS_MR_TABLE)), dim3(MR_BLOCK), 0, st, e0, none, table, (long long)n * RCMVS_MR_TABLE);
     hipLaunchKernelGGL(mr_compare_tile_kernel, dim3(tiles, n), dim3(MR_BLOCK), 0, st, rendered, depth, pixels, th, partial_work, table);
     RCMVS_LAUNCH_TIMED(mr_compare_sum_kernel, dim3(n), dim3(MR_BLOCK), 0, st, none, e1, partial_work, tiles, table);
     return launch_status("mr_compare");

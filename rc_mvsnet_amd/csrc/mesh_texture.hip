@@ -20,7 +20,7 @@
 #include "common.h"
 #include "mesh_texture.h"
 #include "mesh_texture_math.h"
-#include "scan_sort.h"                                            // scan3, radix_hist_kernel, radix_scatter_kernel, zero_u64_kernel
+#include "scan_sort.h"                                            // gid, blocks, buffers_overlap, radix_sort, zero_kernel
 
 #pragma clang fp contract(off)
 
@@ -32,8 +32,6 @@ static_assert(mt::MIN_CLASS == RCMVS_MT_MIN_CLASS && mt::MAX_CLASS == RCMVS_MT_M
 static_assert(mt::PER_CLASS + mt::CLASSES <= RCMVS_MT_STATS && mt::T_SY < RCMVS_MT_TABLE && RCMVS_MT_STATS <= MT_BLOCK, "the tables of mesh_texture.h");
 
 using u64 = unsigned long long;
-
-__device__ inline long long mt_id() { return (long long)blockIdx.x * MT_BLOCK + threadIdx.x; }
 
 __device__ inline mr::Proj mt_project(const double* cam, double near_z, const float* __restrict__ verts, int i) {
     return mr::project(cam, near_z, mr::camera(cam, verts[3 * (size_t)i], verts[3 * (size_t)i + 1], verts[3 * (size_t)i + 2]));
@@ -49,18 +47,8 @@ __device__ inline void mt_count(int what, u64* stats, unsigned* sh) {
 }
 
 // ---- vote ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(MT_BLOCK) void mt_zero_int_kernel(int* __restrict__ p, long long n) {
-    const long long i = mt_id();
-    if (i < n) p[i] = 0;
-}
-
-__global__ __launch_bounds__(MT_BLOCK) void mt_zero_u64_kernel(u64* __restrict__ p, long long n) {
-    const long long i = mt_id();
-    if (i < n) p[i] = 0;
-}
-
 __global__ __launch_bounds__(MT_BLOCK) void mt_count_kernel(const int* __restrict__ face_image, long long pixels, int nf, int* count) {
-    const long long p = mt_id();
+    const long long p = gid();
     if (p >= pixels) return;
     const int f = face_image[p];
     if ((unsigned)f < (unsigned)nf) atomicAdd(&count[f], 1);
@@ -68,7 +56,7 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_count_kernel(const int* __restric
 
 __global__ __launch_bounds__(MT_BLOCK) void mt_best_kernel(const float* __restrict__ verts, const int* __restrict__ faces, int nv, int nf, mr::Cam cam, double near_z,
                                                            int H, int W, unsigned view, const int* __restrict__ count, u64* __restrict__ best) {
-    const long long f = mt_id();
+    const long long f = gid();
     if (f >= nf) return;
     const int n = count[f];
     if (n <= 0) return;
@@ -96,7 +84,7 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_class_kernel(const float* __restr
                                                             const double* __restrict__ cams, double near_z, const u64* __restrict__ best, int shift,
                                                             int* __restrict__ klass, unsigned* __restrict__ key, int* __restrict__ idx, u64* stats) {
     __shared__ unsigned sh[RCMVS_MT_STATS];
-    const long long f = mt_id();
+    const long long f = gid();
     int what = -1, k = 0, capped = 0;
     if (f < nf) {
         const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
@@ -130,7 +118,7 @@ __global__ void mt_table_kernel(const u64* __restrict__ stats, long long* __rest
 // key and order are this call's own work; they are still tested before they are used
 __global__ __launch_bounds__(MT_BLOCK) void mt_texel_kernel(const unsigned* __restrict__ key, const int* __restrict__ order, int nf, const long long* __restrict__ table,
                                                             int* __restrict__ texel) {
-    const long long p = mt_id();
+    const long long p = gid();
     if (p >= nf) return;
     const int f = order[p];
     if ((unsigned)f >= (unsigned)nf) return;
@@ -152,7 +140,7 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_fill_kernel(const float* __restri
                                                            const long long* __restrict__ table, int S, int Sy, int background, unsigned char* __restrict__ atlas,
                                                            int* __restrict__ owner, u64* stats) {
     __shared__ unsigned sh[RCMVS_MT_STATS];
-    const long long m = mt_id();
+    const long long m = gid();
     int what = -1;
     if (m < (long long)S * Sy) {
         const int x = mt::morton_x(m), y = mt::morton_y(m);
@@ -207,7 +195,7 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_fill_kernel(const float* __restri
 __global__ __launch_bounds__(MT_BLOCK) void mt_shade_kernel(const float* __restrict__ verts, const int* __restrict__ faces, int nv, int nf, mr::Cam cam, double near_z,
                                                             int H, int W, const int* __restrict__ face_image, const int* __restrict__ texel,
                                                             const unsigned char* __restrict__ atlas, int S, int Sy, int background, unsigned char* __restrict__ tex_rgb) {
-    const long long p = mt_id(), pixels = (long long)H * W;
+    const long long p = gid(), pixels = (long long)H * W;
     if (p >= pixels) return;
     unsigned char col[3] = {(unsigned char)(background & 255), (unsigned char)((background >> 8) & 255), (unsigned char)((background >> 16) & 255)};
     const int f = face_image[p];
@@ -234,19 +222,6 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_shade_kernel(const float* __restr
     tex_rgb[3 * p] = col[0];
     tex_rgb[3 * p + 1] = col[1];
     tex_rgb[3 * p + 2] = col[2];
-}
-
-static inline unsigned mt_blocks(long long n) { return (unsigned)(n > 0 ? cdiv(n, MT_BLOCK) : 1); }
-
-static bool mt_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
-
-static int mt_overlaps(const char* what, const void* const* ptr, const size_t* len, int outputs, int all) {
-    for (int i = 0; i < outputs; ++i)                                 // every output and work buffer against everything after it
-        for (int j = i + 1; j < all; ++j) RCMVS_REQUIRE(!mt_overlap(ptr[i], len[i], ptr[j], len[j]), "%s: an output or work buffer overlaps another buffer", what);
-    return 0;
 }
 
 static int mt_sizes(const char* what, int nv, int nf) {
@@ -288,20 +263,20 @@ extern "C" int rcmvs_mt_vote_timed(const float* verts, const int* faces, int nv,
     {
         const void* ptr[] = {count, best, verts, faces, face_image};
         const size_t len[] = {(size_t)nf * 4, (size_t)nf * 8, (size_t)nv * 12, (size_t)nf * 12, pixels * (size_t)n * 4};
-        if (int rc = mt_overlaps(what, ptr, len, 2, 5)) return rc;
+        if (int rc = buffers_overlap(what, ptr, len, 2, 5)) return rc;
     }
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
     if (reset) {
-        RCMVS_LAUNCH_TIMED(mt_zero_u64_kernel, dim3(mt_blocks(nf)), dim3(MT_BLOCK), 0, st, e0, none, best, (long long)nf);
+        RCMVS_LAUNCH_TIMED(zero_kernel<u64>, dim3(blocks(nf)), dim3(MT_BLOCK), 0, st, e0, none, best, (long long)nf);
         e0 = none;
     }
     for (int v = 0; v < n; ++v) {
         mr::Cam cam;
         for (int k = 0; k < 16; ++k) cam.c[k] = cams_host[16 * (size_t)v + k];
-        RCMVS_LAUNCH_TIMED(mt_zero_int_kernel, dim3(mt_blocks(nf)), dim3(MT_BLOCK), 0, st, v == 0 ? e0 : none, none, count, (long long)nf);
-        hipLaunchKernelGGL(mt_count_kernel, dim3(mt_blocks((long long)pixels)), dim3(MT_BLOCK), 0, st, face_image + (size_t)v * pixels, (long long)pixels, nf, count);
-        RCMVS_LAUNCH_TIMED(mt_best_kernel, dim3(mt_blocks(nf)), dim3(MT_BLOCK), 0, st, none, v == n - 1 ? e1 : none, verts, faces, nv, nf, cam, near_z, H, W,
+        RCMVS_LAUNCH_TIMED(zero_kernel<int>, dim3(blocks(nf)), dim3(MT_BLOCK), 0, st, v == 0 ? e0 : none, none, count, (long long)nf);
+        hipLaunchKernelGGL(mt_count_kernel, dim3(blocks((long long)pixels)), dim3(MT_BLOCK), 0, st, face_image + (size_t)v * pixels, (long long)pixels, nf, count);
+        RCMVS_LAUNCH_TIMED(mt_best_kernel, dim3(blocks(nf)), dim3(MT_BLOCK), 0, st, none, v == n - 1 ? e1 : none, verts, faces, nv, nf, cam, near_z, H, W,
                            (unsigned)(first_view + v), count, best);
     }
     return launch_status(what);
@@ -335,20 +310,16 @@ extern "C" int rcmvs_mt_layout_timed(const float* verts, const int* faces, int n
         const void* ptr[] = {klass, key_a, idx_a, key_b, order, hist, hist_start, table, texel, stats, verts, faces, best, cams_dev};
         const size_t len[] = {(size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)cells * 4, (size_t)(cells + 1) * 4,
                               (size_t)RCMVS_MT_TABLE * 8, (size_t)n * 24, (size_t)RCMVS_MT_STATS * 8, (size_t)nv * 12, (size_t)n * 12, (size_t)n * 8, (size_t)V * 128};
-        if (int rc = mt_overlaps(what, ptr, len, 10, 14)) return rc;
+        if (int rc = buffers_overlap(what, ptr, len, 10, 14)) return rc;
     }
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(zero_u64_kernel, dim3(1), dim3(MT_BLOCK), 0, st, e0, none, stats, RCMVS_MT_STATS);
-    hipLaunchKernelGGL(mt_class_kernel, dim3(mt_blocks(n)), dim3(MT_BLOCK), 0, st, verts, faces, nv, nf, V, H, W, cams_dev, near_z, best, shift, klass, key_a, idx_a,
+    RCMVS_LAUNCH_TIMED(zero_kernel<u64>, dim3(1), dim3(MT_BLOCK), 0, st, e0, none, stats, (long long)RCMVS_MT_STATS);
+    hipLaunchKernelGGL(mt_class_kernel, dim3(blocks(n)), dim3(MT_BLOCK), 0, st, verts, faces, nv, nf, V, H, W, cams_dev, near_z, best, shift, klass, key_a, idx_a,
                        stats);
-    if (n > 0) {
-        hipLaunchKernelGGL(radix_hist_kernel<unsigned>, dim3((unsigned)nblk), dim3(MT_BLOCK), 0, st, key_a, n, 0, nblk, hist);
-        scan3<int>(hist, cells, hist_start, scan_work, nullptr, st, none, none);
-        hipLaunchKernelGGL(radix_scatter_kernel<unsigned>, dim3((unsigned)nblk), dim3(MT_BLOCK), 0, st, key_a, idx_a, n, 0, nblk, hist_start, key_b, order);
-    }
+    radix_sort<unsigned>(&key_a, &idx_a, &key_b, &order, n, 1, hist, hist_start, scan_work, st);      // one pass: sorted into key_b / order, now *key_a / *idx_a
     hipLaunchKernelGGL(mt_table_kernel, dim3(1), dim3(64), 0, st, stats, table);
-    RCMVS_LAUNCH_TIMED(mt_texel_kernel, dim3(mt_blocks(n)), dim3(MT_BLOCK), 0, st, none, e1, key_b, order, nf, table, texel);
+    RCMVS_LAUNCH_TIMED(mt_texel_kernel, dim3(blocks(n)), dim3(MT_BLOCK), 0, st, none, e1, key_a, idx_a, nf, table, texel);
     return launch_status(what);
 }
 
@@ -379,12 +350,12 @@ extern "C" int rcmvs_mt_fill_timed(const float* verts, const unsigned char* rgb,
         const void* ptr[] = {atlas, owner, stats, verts, rgb, faces, cams_dev, images, best, order, table};
         const size_t len[] = {texels * 3, texels * 4, (size_t)RCMVS_MT_STATS * 8, (size_t)nv * 12, (size_t)nv * 3, (size_t)nf * 12, (size_t)V * 128,
                               (size_t)V * H * W * 3, (size_t)nf * 8, (size_t)nf * 4, (size_t)RCMVS_MT_TABLE * 8};
-        if (int rc = mt_overlaps(what, ptr, len, 3, 11)) return rc;
+        if (int rc = buffers_overlap(what, ptr, len, 3, 11)) return rc;
     }
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
-    RCMVS_LAUNCH_TIMED(zero_u64_kernel, dim3(1), dim3(MT_BLOCK), 0, st, e0, none, stats + mt::TEX_IMAGE, 4);
-    RCMVS_LAUNCH_TIMED(mt_fill_kernel, dim3(mt_blocks((long long)texels)), dim3(MT_BLOCK), 0, st, none, e1, verts, rgb, faces, nv, nf, V, H, W, cams_dev, near_z, images,
+    RCMVS_LAUNCH_TIMED(zero_kernel<u64>, dim3(1), dim3(MT_BLOCK), 0, st, e0, none, stats + mt::TEX_IMAGE, 4ll);
+    RCMVS_LAUNCH_TIMED(mt_fill_kernel, dim3(blocks((long long)texels)), dim3(MT_BLOCK), 0, st, none, e1, verts, rgb, faces, nv, nf, V, H, W, cams_dev, near_z, images,
                        best, order, table, S, Sy, background, atlas, owner, stats);
     return launch_status(what);
 }
@@ -413,14 +384,14 @@ extern "C" int rcmvs_mt_shade_timed(const float* verts, const int* faces, int nv
     {
         const void* ptr[] = {tex_rgb, verts, faces, face_image, texel, atlas};
         const size_t len[] = {all * 3, (size_t)nv * 12, (size_t)nf * 12, all * 4, (size_t)nf * 24, (size_t)S * Sy * 3};
-        if (int rc = mt_overlaps(what, ptr, len, 1, 6)) return rc;
+        if (int rc = buffers_overlap(what, ptr, len, 1, 6)) return rc;
     }
     hipStream_t st = as_stream(stream);
     hipEvent_t e0 = static_cast<hipEvent_t>(ev0), e1 = static_cast<hipEvent_t>(ev1), none = nullptr;
     for (int v = 0; v < n; ++v) {
         mr::Cam cam;
         for (int k = 0; k < 16; ++k) cam.c[k] = cams_host[16 * (size_t)v + k];
-        RCMVS_LAUNCH_TIMED(mt_shade_kernel, dim3(mt_blocks((long long)pixels)), dim3(MT_BLOCK), 0, st, v == 0 ? e0 : none, v == n - 1 ? e1 : none, verts, faces, nv, nf,
+        RCMVS_LAUNCH_TIMED(mt_shade_kernel, dim3(blocks((long long)pixels)), dim3(MT_BLOCK), 0, st, v == 0 ? e0 : none, v == n - 1 ? e1 : none, verts, faces, nv, nf,
                            cam, near_z, H, W, face_image + (size_t)v * pixels, texel, atlas, S, Sy, background, tex_rgb + (size_t)v * pixels * 3);
     }
     return launch_status(what);

@@ -21,23 +21,12 @@
 #include "common.h"
 #include "pc_register.h"
 #include "pc_register_math.h"
+#include "pointcloud_scan.h"                                      // pc_scan
 #include "scan_sort.h"                                            // radix_hist_kernel, radix_scatter_kernel
 
 #pragma clang fp contract(off)
 
 namespace rcmvs {
-
-// pointcloud.hip's multi-block exclusive scan (in[0..n) -> out[0..n), out[n] = total; bsum: ceil(n / RCMVS_PC_SCAN_TILE) + 1 ints)
-__global__ void pc_scan_reduce_kernel(const int* __restrict__ in, int n, int* __restrict__ bsum);
-__global__ void pc_scan_bsums_kernel(int* __restrict__ bsum, int nb);
-__global__ void pc_scan_add_kernel(const int* __restrict__ in, int n, const int* __restrict__ bsum, int nb, int* __restrict__ out);
-
-static void pcr_scan(const int* in, int n, int* bsum, int* out, hipStream_t st) {
-    const int nb = (int)cdiv(n, RCMVS_PC_SCAN_TILE);
-    hipLaunchKernelGGL(pc_scan_reduce_kernel, dim3(nb), dim3(256), 0, st, in, n, bsum);
-    hipLaunchKernelGGL(pc_scan_bsums_kernel, dim3(1), dim3(1024), 0, st, bsum, nb);
-    hipLaunchKernelGGL(pc_scan_add_kernel, dim3(nb), dim3(256), 0, st, in, n, bsum, nb, out);
-}
 
 constexpr int PCR_BLOCK = 256;
 constexpr int PCR_WAVES = PCR_BLOCK / WAVE;
@@ -317,7 +306,7 @@ extern "C" int rcmvs_pc_crop(const float* pts, long long n, const double* transf
     int* offsets = work + nblk;
     int* bsum = offsets + nblk + 1;
     hipLaunchKernelGGL(pcr_crop_count_kernel, dim3(nblk), dim3(PCR_BLOCK), 0, st, c, pts, (int)n, flags, counts);
-    pcr_scan(counts, nblk, bsum, offsets, st);
+    pc_scan(counts, nblk, bsum, offsets, st);
     hipLaunchKernelGGL(pcr_crop_scatter_kernel, dim3(nblk), dim3(PCR_BLOCK), 0, st, c, pts, (int)n, offsets, kept);
     return launch_status("pc_crop");
 }
@@ -348,11 +337,11 @@ extern "C" int rcmvs_pc_voxel_sort(const float* pts, long long n, const double* 
         unsigned long long* kout = p & 1 ? key_a : key_b;
         int* iout = p & 1 ? idx_a : idx_b;
         hipLaunchKernelGGL(radix_hist_kernel<unsigned long long>, dim3(nblk), dim3(PCR_BLOCK), 0, st, kin, n, 8 * p, (long long)nblk, hist);
-        pcr_scan(hist, 256 * nblk, scan_work, hist_start, st);
+        pc_scan(hist, 256 * nblk, scan_work, hist_start, st);
         hipLaunchKernelGGL(radix_scatter_kernel<unsigned long long>, dim3(nblk), dim3(PCR_BLOCK), 0, st, kin, iin, n, 8 * p, (long long)nblk, hist_start, kout, iout);
     }
     hipLaunchKernelGGL(pcr_voxel_head_kernel, dim3(nblk), dim3(PCR_BLOCK), 0, st, key_a, (int)n, head);
-    pcr_scan(head, (int)n, scan_work, head_start, st);
+    pc_scan(head, (int)n, scan_work, head_start, st);
     return launch_status("pc_voxel_sort");
 }
 

@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "pointcloud_math.h"
+#include "pointcloud_scan.h"                                      // pc_scan, defined here
 
 namespace rcmvs {
 
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(PC_BLOCK) void pc_scan_add_kernel(const int* __rest
     if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = bsum[nb];
 }
 
-static void pc_scan(const int* in, int n, int* bsum, int* out, hipStream_t st) {
+void pc_scan(const int* in, int n, int* bsum, int* out, hipStream_t st) {
     const int nb = (int)cdiv(n, PC_SCAN_TILE);
     hipLaunchKernelGGL(pc_scan_reduce_kernel, dim3(nb), dim3(PC_BLOCK), 0, st, in, n, bsum);
     hipLaunchKernelGGL(pc_scan_bsums_kernel, dim3(1), dim3(1024), 0, st, bsum, nb);

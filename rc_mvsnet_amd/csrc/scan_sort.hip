@@ -1,13 +1,15 @@
-// The one three-level scan and the one radix pass of the mesh kernels (declared in scan_sort.h; callers: mesh_clean.hip,
-// mesh_decimate.hip, mesh_holes.hip, and pc_register.hip for the radix pass).
+// The one three-level scan, the one radix sort and the small kernels around them that the mesh kernels share (declared in
+// scan_sort.h; callers: mesh_clean.hip, mesh_decimate.hip, mesh_holes.hip, mesh_normals.hip, mesh_texture.hip, and pc_register.hip
+// for the radix pass).
 //
 //   scan    Flags or counts -> exclusive prefix sums in three levels: tiles of 2048, 2048 tile sums, at most 1024 top sums by one
 //           thread; 64-bit above the tile level.  The work area holds the top sums (uint64), then one unsigned per tile.
 //   radix   Per-block digit histograms in LDS, digit-major (digit, block) table; after the caller's scan of that table a stable
 //           scatter whose in-block rank comes from wave ballots (the keys of the same digit in the lanes and waves before).
+//   sort    radix_sort: the loop hist -> scan3 of the table -> scatter -> swap buffers, as many passes as radix_passes says.
+//   seg     segments_kernel: one thread per sorted key writes where its key's run starts or ends.
+//   zero    zero_kernel: one thread per element.
 // gfx950 only; __syncthreads, ballots, plain loads and stores and integer LDS atomics (tests/emu compiles this file too).
-#include <cstdint>
-
 #include "scan_sort.h"
 #include "tsdf_mesh_cells.h"                                      // tm_block_sum, tm_block_exclusive (256 threads)
 
@@ -102,9 +104,14 @@ int scan_work_check(const char* what, const int* scan_work) {
     return 0;
 }
 
-__global__ __launch_bounds__(SS_BLOCK) void zero_u64_kernel(u64* __restrict__ p, int n) {
-    if (blockIdx.x == 0 && (int)threadIdx.x < n) p[threadIdx.x] = 0;
+template <class T>
+__global__ __launch_bounds__(SS_BLOCK) void zero_kernel(T* __restrict__ p, long long n) {
+    const long long i = gid();
+    if (i < n) p[i] = 0;
 }
+
+template __global__ void zero_kernel<int>(int* __restrict__, long long);
+template __global__ void zero_kernel<u64>(u64* __restrict__, long long);
 
 // ---- one pass of the radix sort of (key, index) pairs --------------------------------------------------------------------------
 template <class K>
@@ -159,5 +166,40 @@ template __global__ void radix_scatter_kernel<u64>(const u64* __restrict__, cons
                                                    u64* __restrict__, int* __restrict__);
 template __global__ void radix_scatter_kernel<unsigned>(const unsigned* __restrict__, const int* __restrict__, long long, int, long long,
                                                         const int* __restrict__, unsigned* __restrict__, int* __restrict__);
+
+// ---- the passes ---------------------------------------------------------------------------------------------------------------------
+int radix_passes(u64 largest_key) {
+    int bits = 0;
+    for (u64 top = largest_key; top; top >>= 1) ++bits;
+    const int passes = (bits + 7) / 8;
+    return passes < 1 ? 1 : passes;
+}
+
+template <class K>
+void radix_sort(K** ka, int** ia, K** kb, int** ib, long long n, int passes, int* hist, int* hist_start, int* scan_work, hipStream_t st) {
+    if (n <= 0) return;
+    const long long nblk = cdiv(n, SS_BLOCK);
+    hipEvent_t none = nullptr;
+    for (int p = 0; p < passes; ++p) {
+        hipLaunchKernelGGL(radix_hist_kernel<K>, dim3((unsigned)nblk), dim3(SS_BLOCK), 0, st, *ka, n, 8 * p, nblk, hist);
+        scan3<int>(hist, 256 * nblk, hist_start, scan_work, nullptr, st, none, none);
+        hipLaunchKernelGGL(radix_scatter_kernel<K>, dim3((unsigned)nblk), dim3(SS_BLOCK), 0, st, *ka, *ia, n, 8 * p, nblk, hist_start, *kb, *ib);
+        K* tk = *ka; *ka = *kb; *kb = tk;
+        int* ti = *ia; *ia = *ib; *ib = ti;
+    }
+}
+
+template void radix_sort<u64>(u64**, int**, u64**, int**, long long, int, int*, int*, int*, hipStream_t);
+template void radix_sort<unsigned>(unsigned**, int**, unsigned**, int**, long long, int, int*, int*, int*, hipStream_t);
+
+// ---- segments of the sorted keys ----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(SS_BLOCK) void segments_kernel(const unsigned* __restrict__ key, long long n, int m, int* __restrict__ seg) {
+    const long long i = gid();
+    if (i >= n) return;
+    const unsigned k = key[i];
+    if (k >= (unsigned)m) return;
+    if (i == 0 || key[i - 1] != k) seg[2 * (size_t)k] = (int)i;
+    if (i == n - 1 || key[i + 1] != k) seg[2 * (size_t)k + 1] = (int)(i + 1);
+}
 
 }  // namespace rcmvs
