@@ -41,14 +41,15 @@ __global__ __launch_bounds__(FU_BLOCK) void fuse_view_kernel(
     }
     const double avg = (double)(acc + d_ref) / (double)(geo_sum + 1);
     const bool photo = conf[p] > prob_thresh, geo = geo_sum >= num_consistent;
-    masks[p] = photo; masks[plane + p] = geo; masks[2 * plane + p] = photo && geo;
+    masks[p] = photo; masks[plane + p] = geo; masks[2ll * plane + p] = photo && geo;
     depth_avg[p] = (float)avg;
     double wpt[3];
     fu::world_point(mats, x, y, avg, wpt);
-    xyz[p * 3 + 0] = (float)wpt[0]; xyz[p * 3 + 1] = (float)wpt[1]; xyz[p * 3 + 2] = (float)wpt[2];
+    const long long p3 = (long long)p * 3;                       // H*W may reach 2^30 - 1: p * 3 does not fit 32 bits
+    xyz[p3 + 0] = (float)wpt[0]; xyz[p3 + 1] = (float)wpt[1]; xyz[p3 + 2] = (float)wpt[2];
     if (img) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) rgb[p * 3 + c] = (unsigned char)(int)(img[p * 3 + c] * 255.0f);
+        for (int c = 0; c < 3; ++c) rgb[p3 + c] = (unsigned char)(int)(img[p3 + c] * 255.0f);
     }
 }
 

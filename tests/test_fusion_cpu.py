@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import fusion_cases as FC
+import fusion_oracle as FO
 from oracle import fusion as O
 from rc_mvsnet_amd import _lib, fusion, scan_io, synthetic
 
@@ -254,3 +256,66 @@ def test_kernel_arithmetic_edge_cases(case_name, harness):
         assert not masks[1][3:9, 5:11].any()                    # a hole in the reference map is never consistent
     if case_name == "source_out_of_frame":
         assert not dg[1].any()
+
+
+# ---- the exact oracle (tests/fusion_oracle.py) pinned from both sides: the reference-order oracle on the golden scan, the g++ loop
+# ---- harness around csrc/fusion_math.h on every case of tests/fusion_cases.py
+def test_exact_oracle_agrees_with_the_reference_order_oracle_on_the_golden_scan():
+    """oracle/fusion.py (pinned by tests/golden/fusion.npz) sums and multiplies in numpy's matrix order, the exact oracle in the kernel's:
+    within the bounds test_kernel_arithmetic_matches_oracle sets for the harness, with the flips printed"""
+    s = scan()
+    V, H, W = s["depth"].shape
+    total_flips = 0
+    for ref, srcs in s["pairs"]:
+        c = FC.make_case(s["depth"], ref, srcs, s["conf"][ref], s["img"][ref].astype(np.float32) / 255.0, s["K"], s["E"], PROB, NCONS, DIST, DEPTH)
+        e = FC.oracle(c)
+        r = O.fuse_view(s["depth"][ref], s["conf"][ref], c["img"], s["K"][ref], s["E"][ref], [s["depth"][i] for i in srcs],
+                        [s["K"][i] for i in srcs], [s["E"][i] for i in srcs], PROB, NCONS, DIST, DEPTH)
+        masks = e["masks"].astype(bool)
+        assert np.array_equal(masks[0], r["photo"])
+        total_flips += int((masks[1] != r["geo"]).sum())
+        same = masks[2] == r["final"]
+        assert np.allclose(e["depth_avg"][same], r["depth_avg"].astype(np.float32)[same], rtol=1e-6)
+        both = masks[2] & r["final"]
+        want = np.zeros((H, W, 3), np.float32)
+        want[r["final"]] = r["xyz"]
+        assert np.allclose(e["xyz"][both], want[both], rtol=1e-5, atol=1e-3)
+        wrgb = np.zeros((H, W, 3), np.uint8)
+        wrgb[r["final"]] = r["rgb"]
+        assert np.array_equal(e["rgb"][both], wrgb[both])
+        for n, src in enumerate(srcs):
+            m, back, xs, ys = O.check_geometric_consistency(s["depth"][ref], s["K"][ref], s["E"][ref], s["depth"][src], s["K"][src], s["E"][src], DIST, DEPTH)
+            assert np.allclose(e["xy_src"][n, ..., 0], xs, rtol=1e-6, atol=1e-4) and np.allclose(e["xy_src"][n, ..., 1], ys, rtol=1e-6, atol=1e-4)
+            agree = e["geo"][n].astype(bool) == m
+            assert agree.mean() > 0.995
+            assert np.allclose(e["depth_reprojected"][n][agree], back[agree], rtol=1e-6, atol=1e-3)
+    print("exact oracle against the reference-order oracle on the golden scan: %d geo-mask flips" % total_flips)
+    assert total_flips <= 3
+
+
+def harness_run(harness, c):
+    """h_fuse_view on a case of tests/fusion_cases.py, every output buffer pre-filled -> the outputs as FC.run gives them"""
+    V, H, W = c["depth_all"].shape
+    N = len(c["srcs"])
+    out = {"masks": np.full((3, H, W), 99, np.uint8), "depth_avg": np.full((H, W), -7.0, np.float32), "xyz": np.full((H, W, 3), -7.0, np.float32),
+           "rgb": None if c["img"] is None else np.full((H, W, 3), 99, np.uint8), "depth_reprojected": np.full((N, H, W), -7.0, np.float32),
+           "geo": np.full((N, H, W), 99, np.uint8), "xy_src": np.full((N, H, W, 2), -7.0, np.float32)}
+    idx = np.array(c["srcs"], np.int32)
+    harness.h_fuse_view(_p(c["depth_all"]), c["ref"], _p(idx), _p(c["conf"]), _p(c["img"]), _p(c["mats"]), ctypes.c_float(c["prob"]), int(c["ncons"]),
+                        ctypes.c_double(c["dist"]), ctypes.c_float(c["depth_t"]), _p(out["masks"]), _p(out["depth_avg"]), _p(out["xyz"]), _p(out["rgb"]),
+                        _p(out["depth_reprojected"]), _p(out["geo"]), _p(out["xy_src"]), N, H, W)
+    return out
+
+
+@pytest.mark.parametrize("name", list(FC.CASES))
+def test_exact_oracle_equals_the_harness_in_every_bit(name, harness):
+    """every case the GPU and the emulation run: masks, depth_avg, xyz, rgb and the three debug outputs at every pixel"""
+    FC.assert_outputs(harness_run(harness, FC.case(name)), FC.reference(name), name)
+
+
+def test_exact_oracle_equals_the_harness_on_whole_scans(harness):
+    """every reference view of the golden-sized DTU scan"""
+    s = scan()
+    for ref, srcs in s["pairs"]:
+        c = FC.make_case(s["depth"], ref, srcs, s["conf"][ref], s["img"][ref].astype(np.float32) / 255.0, s["K"], s["E"], PROB, NCONS, DIST, DEPTH)
+        FC.assert_outputs(harness_run(harness, c), FC.oracle(c), ("golden scan", ref))

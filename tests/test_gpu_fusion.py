@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import fusion_cases as FC
 from oracle import fusion as O
 from rc_mvsnet_amd import _lib, fusion, synthetic
 
@@ -133,3 +134,32 @@ def test_filter_depth_tanks_matches_reference(tmp_path):
     with pytest.raises(_lib.RcmvsError):
         fusion.filter_depth_tanks(scan_folder, out_folder, str(tmp_path / "x.ply"), pix, dth, photo, (w + 32, h), (ow, oh), int(ncons), V, "Horse",
                                   verbose=False)
+
+
+# ---- bit for bit against the exact oracle (tests/fusion_oracle.py), on the cases of tests/fusion_cases.py: every output at every pixel,
+# ---- no flipped mask allowed.  tests/test_fusion_emu_cpu.py runs the same functions on the CPU emulation.
+def test_exact_friendly_scan():
+    FC.check_friendly(DEV)
+
+
+@pytest.mark.parametrize("group", [g for g in FC.GROUPS if g != "friendly"])
+def test_exact_hostile_cases(group):
+    """holes and non-finite depths, source geometry, border positions, threshold knife edges, source counts, shapes, colour levels"""
+    FC.check_group(DEV, group)
+
+
+@pytest.mark.parametrize("n", FC.COMPACT_SIZES)
+def test_exact_compaction_round_the_scan_boundaries(n):
+    FC.check_compaction(DEV, n)
+
+
+def test_exact_refusals_before_any_launch():
+    FC.check_refusals(DEV)
+
+
+def test_filter_depth_is_the_exact_oracle(tmp_path):
+    FC.check_filter_depth(DEV, tmp_path)
+
+
+def test_filter_depth_tanks_is_the_exact_oracle(tmp_path):
+    FC.check_filter_depth_tanks(DEV, tmp_path)
