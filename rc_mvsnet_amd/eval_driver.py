@@ -130,7 +130,8 @@ def run_scans(model, args, device, rank, world):
                                               min_fraction=args.mesh_min_fraction, keep_largest=args.mesh_keep_largest, smooth=args.mesh_smooth,
                                               decimate_voxels=args.mesh_decimate_voxels, fill_holes=args.mesh_fill_holes,
                                               render_dir=None if args.mesh_render is None else os.path.join(args.mesh_render, scan),
-                                              normals=args.mesh_normals, **({"texture": True} if args.mesh_texture else {}))
+                                              normals=args.mesh_normals, **({"texture": True} if args.mesh_texture else {}),
+                                              **({"simplify_ratio": args.mesh_simplify_ratio} if args.mesh_simplify_ratio else {}))
                 print(json.dumps(summary))
             if args.dtu_gt:
                 score_scan(args, scan, device)
@@ -223,7 +224,8 @@ def run_tanks(model, args, device, rank, world):
                                                 keep_largest=args.mesh_keep_largest, smooth=args.mesh_smooth,
                                                 decimate_voxels=args.mesh_decimate_voxels, fill_holes=args.mesh_fill_holes,
                                                 render_dir=None if args.mesh_render is None else os.path.join(args.mesh_render, scene),
-                                                normals=args.mesh_normals, **({"texture": True} if args.mesh_texture else {}))
+                                                normals=args.mesh_normals, **({"texture": True} if args.mesh_texture else {}),
+                                              **({"simplify_ratio": args.mesh_simplify_ratio} if args.mesh_simplify_ratio else {}))
             print(json.dumps(summary))
         del depth_maps, conf_maps
     if times:
@@ -289,6 +291,8 @@ def main(argv=None):
                          "to it as <name>.png; with --mesh-render also the textured views")
     ap.add_argument("--mesh-decimate-voxels", type=float, default=0.0,
                     help="--mesh: decimation (rc_mvsnet_amd.mesh_decimate) after the clean-up, cells of this many voxels")
+    ap.add_argument("--mesh-simplify-ratio", type=float, default=0.0,
+                    help="--mesh: edge collapse (rc_mvsnet_amd.mesh_simplify) after the clean-up and the decimation, down to this fraction of the faces")
     ap.add_argument("--dtu-gt", default=None, help="DTU MVS_Data folder: after --filter, score each fused cloud (accuracy / completeness, "
                                                    "rc_mvsnet_amd.dtu_eval)")
     ap.add_argument("--prob_thres", type=float, default=0.8)

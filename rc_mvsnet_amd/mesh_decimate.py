@@ -13,8 +13,8 @@ there is no per-vertex or per-face host pass.
 
     python -m rc_mvsnet_amd.mesh_decimate --in a.ply --out b.ply --cell 0.004
 
-Limits: no feature-preserving edge collapse (one vertex per occupied cell, so two sheets closer than a cell merge and thin parts
-can collapse); clustering can create non-manifold edges, which the stats count; at most 2^21 cells per axis; at most 2^31 - 256
+Limits: clustering preserves no features (one vertex per occupied cell, so two sheets closer than a cell merge and thin parts
+can collapse; rc_mvsnet_amd.mesh_simplify collapses edges instead); clustering can create non-manifold edges, which the stats count; at most 2^21 cells per axis; at most 2^31 - 256
 vertices and (2^31 - 256) / 3 faces.  No CPU fallback."""
 import argparse
 import ctypes

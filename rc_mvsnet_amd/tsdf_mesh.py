@@ -404,7 +404,7 @@ def filtered_views_tanks(scan_folder, out_folder, geo_pixel_thres, geo_depth_thr
 def mesh_scan_tanks(scan_folder, out_folder, meshfilename, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes, geo_mask_thres,
                     n_views=None, scan="", device="cuda:0", depth_maps=None, conf_maps=None, voxel=None, resolution=1024, trunc_voxels=3.0,
                     min_weight=1, bounds=None, min_faces=0, min_fraction=0.0, keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0,
-                    render_dir=None, normals=None, texture=False, texture_size=None):
+                    render_dir=None, normals=None, texture=False, texture_size=None, simplify_faces=0, simplify_ratio=0.0, simplify_max_error=None):
     """The mesh counterpart of fusion.filter_depth_tanks, with its arguments: the scene's filtered ``depth_avg`` maps integrated into
     a SparseTsdfVolume (always sparse: these are the scenes a dense box does not fit) and meshed into ``meshfilename``.  Where no
     point survives the filter and no bounds are given there is nothing to put a grid round: the PLY is written empty, as
@@ -419,6 +419,7 @@ def mesh_scan_tanks(scan_folder, out_folder, meshfilename, geo_pixel_thres, geo_
                 "skipped_pixels": 0, "empty": "no point survives the filter"}
     return _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, True, device,
                        mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth, fill_holes), **_decimate_argument(decimate_cell, decimate_voxels),
+                       **_simplify_argument(simplify_faces, simplify_ratio, simplify_max_error),
                        **_render_argument(render_dir), **_normals_argument(normals), **_texture_argument(texture, texture_size))
 
 
@@ -426,6 +427,15 @@ def _decimate_argument(cell, voxels):
     """-> the keyword that hands mesh_decimate.decimate_options to _mesh_views; nothing at all when neither option is given"""
     options = mesh_decimate.decimate_options(cell, voxels)
     return {} if options is None else {"decimate": options}
+
+
+def _simplify_argument(faces, ratio, max_error):
+    """-> the keyword that hands mesh_simplify.simplify_options to _mesh_views; nothing at all when neither target is given"""
+    if not faces and not ratio and max_error is None:
+        return {}
+    from . import mesh_simplify
+    options = mesh_simplify.simplify_options(faces, ratio, max_error)
+    return {} if options is None else {"simplify": options}
 
 
 def _render_argument(render_dir):
@@ -493,9 +503,10 @@ def plan_sparse_grid(lo, hi, voxel=None, resolution=1024, trunc_voxels=3.0, pad=
 
 
 def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, sparse, device, clean=None, decimate=None, render=None,
-                normals=None, texture=None):
+                normals=None, texture=None, simplify=None):
     """Plans the grid, integrates the filtered views, extracts, cleans the mesh when ``clean`` (the keyword arguments of
-    mesh_clean.clean_mesh) is given, then decimates it when ``decimate`` (of mesh_decimate.decimate_options) is given, and writes
+    mesh_clean.clean_mesh) is given, then decimates it when ``decimate`` (of mesh_decimate.decimate_options) is given, then collapses
+    edges when ``simplify`` (of mesh_simplify.simplify_options) is given, and writes
     the PLY; with ``render`` (a folder) renders the written mesh into the views it was fused from (rc_mvsnet_amd.mesh_render) and
     compares it with their filtered depth maps; with ``normals`` (of mesh_normals.normals_options) computes the vertex normals of
     the final mesh, writes them into the PLY and hands them to the render; with ``texture`` (of mesh_texture.texture_options) textures
@@ -528,6 +539,9 @@ def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight
     if decimate is not None:
         verts, faces, rgb, stats = mesh_decimate.decimate_mesh_path(verts, faces, rgb, decimate, voxel)
         extra["decimate"] = stats
+    if simplify is not None:
+        from . import mesh_simplify
+        verts, faces, rgb, extra["simplify"] = mesh_simplify.simplify(verts, faces, rgb, **simplify)
     os.makedirs(os.path.dirname(os.path.abspath(meshfilename)), exist_ok=True)
     vertex_normals = None
     if normals is not None:
@@ -558,13 +572,15 @@ def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight
 def mesh_scan(pair_folder, scan_folder, out_folder, meshfilename, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage=3,
               voxel=None, resolution=256, trunc_voxels=3.0, min_weight=1, bounds=None, device="cuda:0", sparse=False, min_faces=0, min_fraction=0.0,
               keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0, render_dir=None, normals=None, texture=False,
-              texture_size=None):
+              texture_size=None, simplify_faces=0, simplify_ratio=0.0, simplify_max_error=None):
     """Mesh one scan laid out as fusion.filter_depth reads it into ``meshfilename``.  bounds: (xmin, ymin, zmin, xmax, ymax, zmax),
     default the bounding box of the points that survive the filter, padded by the truncation distance.  sparse: a SparseTsdfVolume
     planned by plan_sparse_grid (resolution None: 1024); the summary then also reports bdims, active_blocks, allocated_voxels and
     skipped_pixels.  min_faces, min_fraction, keep_largest, smooth, fill_holes: any of them given, mesh_clean.clean_mesh runs on the
     extracted mesh and the summary gains its stats as "clean" (with fill_holes, "holes" among them).  decimate_cell (world units) or decimate_voxels (in voxels of the volume), not
-    both: mesh_decimate.decimate runs after the clean-up and the summary gains its stats as "decimate".  render_dir: the written mesh is
+    both: mesh_decimate.decimate runs after the clean-up and the summary gains its stats as "decimate".  simplify_faces (a face count) or
+    simplify_ratio (a fraction of the valid faces), not both, with simplify_max_error: mesh_simplify.simplify runs after the clean-up and the
+    clustering, before normals and texture, and the summary gains its stats as "simplify".  render_dir: the written mesh is
     rendered into the views it was fused from (mesh_render.render_views: depth_mesh/ and render/ under that folder) and compared with
     their filtered depth maps; the summary gains the summed table as "render".  normals ('area' or 'sphere'): mesh_normals.vertex_normals
     runs last, on the mesh that is written; the PLY's vertex records gain nx ny nz, the summary gains the stats as "normals", and a
@@ -576,6 +592,7 @@ def mesh_scan(pair_folder, scan_folder, out_folder, meshfilename, prob_threshold
         resolution = 1024 if sparse else 256
     return _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, bool(sparse), device,
                        mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth, fill_holes), **_decimate_argument(decimate_cell, decimate_voxels),
+                       **_simplify_argument(simplify_faces, simplify_ratio, simplify_max_error),
                        **_render_argument(render_dir), **_normals_argument(normals), **_texture_argument(texture, texture_size))
 
 
@@ -604,6 +621,10 @@ def main(argv=None):
     dec = ap.add_mutually_exclusive_group()
     dec.add_argument("--decimate-cell", type=float, default=0.0, help="decimation: edge of the clustering cells, world units")
     dec.add_argument("--decimate-voxels", type=float, default=0.0, help="decimation: edge of the clustering cells in voxels of the volume")
+    sim = ap.add_mutually_exclusive_group()
+    sim.add_argument("--simplify-faces", type=int, default=0, help="edge collapse (rc_mvsnet_amd.mesh_simplify) down to this many faces")
+    sim.add_argument("--simplify-ratio", type=float, default=0.0, help="edge collapse down to this fraction of the faces")
+    ap.add_argument("--simplify-max-error", type=float, default=None, help="edge collapse: no collapse above this cost (needs one of the two targets)")
     ap.add_argument("--render", default=None, metavar="DIR", help="render the written mesh into the views it was fused from (rc_mvsnet_amd.mesh_render): "
                                                                   "DIR/depth_mesh/*.pfm, DIR/render/*.png, and \"render\" in the summary")
     ap.add_argument("--normals", choices=("area", "sphere"), default=None, help="write oriented vertex normals (rc_mvsnet_amd.mesh_normals) into the PLY; "
@@ -617,7 +638,9 @@ def main(argv=None):
                         num_stage=a.num_stage, voxel=a.voxel, resolution=a.resolution, trunc_voxels=a.trunc_voxels, min_weight=a.min_weight,
                         bounds=a.bounds, device=a.device, sparse=a.sparse, min_faces=a.min_faces, min_fraction=a.min_fraction,
                         keep_largest=a.keep_largest, smooth=a.smooth, decimate_cell=a.decimate_cell, decimate_voxels=a.decimate_voxels,
-                        fill_holes=a.fill_holes, render_dir=a.render, normals=a.normals, **({"texture": True, "texture_size": a.texture_size} if a.texture else {}))
+                        fill_holes=a.fill_holes, render_dir=a.render, normals=a.normals, **({"texture": True, "texture_size": a.texture_size} if a.texture else {}),
+                        **({"simplify_faces": a.simplify_faces, "simplify_ratio": a.simplify_ratio, "simplify_max_error": a.simplify_max_error}
+                           if (a.simplify_faces or a.simplify_ratio or a.simplify_max_error is not None) else {}))
     print(json.dumps(summary))
     return summary
 
