@@ -118,9 +118,13 @@ def run_scans(model, args, device, rank, world):
                 writer.submit(save_reference_view, args.outdir, name, cam, item["imgs"][0].cpu())
         if args.filter:
             folder = os.path.join(args.outdir, scan)
+            fstats = {}
             fusion.filter_depth(os.path.join(args.testpath, scan), folder, folder, os.path.join(args.outdir, scan + ".ply"),
                                 args.prob_thres, args.num_consistency, args.img_dist_thres, args.depth_thres,
-                                num_stage=nstage, device=str(device))
+                                num_stage=nstage, device=str(device), **(dict(args.fusion_options, stats=fstats) if args.fusion_options else {}))
+            if args.fusion_options:
+                print(json.dumps({"scan": scan, "fusion": fusion.fusion_summary(args.fusion_options, fstats,
+                                                                                (args.num_consistency, args.img_dist_thres, args.depth_thres))}))
             if args.mesh:
                 from . import tsdf_mesh
                 summary = tsdf_mesh.mesh_scan(os.path.join(args.testpath, scan), folder, folder, os.path.join(args.outdir, scan + "_mesh.ply"),
@@ -131,7 +135,8 @@ def run_scans(model, args, device, rank, world):
                                               decimate_voxels=args.mesh_decimate_voxels, fill_holes=args.mesh_fill_holes,
                                               render_dir=None if args.mesh_render is None else os.path.join(args.mesh_render, scan),
                                               normals=args.mesh_normals, **({"texture": True} if args.mesh_texture else {}),
-                                              **({"simplify_ratio": args.mesh_simplify_ratio} if args.mesh_simplify_ratio else {}))
+                                              **({"simplify_ratio": args.mesh_simplify_ratio} if args.mesh_simplify_ratio else {}),
+                                              **mesh_fusion_options(args))
                 print(json.dumps(summary))
             if args.dtu_gt:
                 score_scan(args, scan, device)
@@ -210,9 +215,14 @@ def run_tanks(model, args, device, rank, world):
                     depth_maps[view], conf_maps[view] = depth, conf
         views_done += len(ds)
         f = fusion.TANKS_FILTER[args.split][scene]
+        fstats = {}
         fusion.filter_depth_tanks(os.path.join(args.testpath, args.split, scene), os.path.join(args.outdir, scene), ply, f["geo_pixel_thres"],
                                   f["geo_depth_thres"], f["photo_thres"], img_wh, f["image_size"], f["geo_mask_thres"], args.num_view, scene,
-                                  device=str(device), depth_maps=depth_maps, conf_maps=conf_maps)
+                                  device=str(device), depth_maps=depth_maps, conf_maps=conf_maps,
+                                  **(dict(args.fusion_options, stats=fstats) if args.fusion_options else {}))
+        if args.fusion_options:
+            print(json.dumps({"scene": scene, "fusion": fusion.fusion_summary(args.fusion_options, fstats,
+                                                                               (f["geo_mask_thres"], f["geo_pixel_thres"], f["geo_depth_thres"]))}))
         if args.mesh:
             from . import tsdf_mesh
             summary = tsdf_mesh.mesh_scan_tanks(os.path.join(args.testpath, args.split, scene), os.path.join(args.outdir, scene),
@@ -225,13 +235,23 @@ def run_tanks(model, args, device, rank, world):
                                                 decimate_voxels=args.mesh_decimate_voxels, fill_holes=args.mesh_fill_holes,
                                                 render_dir=None if args.mesh_render is None else os.path.join(args.mesh_render, scene),
                                                 normals=args.mesh_normals, **({"texture": True} if args.mesh_texture else {}),
-                                              **({"simplify_ratio": args.mesh_simplify_ratio} if args.mesh_simplify_ratio else {}))
+                                              **({"simplify_ratio": args.mesh_simplify_ratio} if args.mesh_simplify_ratio else {}),
+                                                **mesh_fusion_options(args))
             print(json.dumps(summary))
         del depth_maps, conf_maps
     if times:
         warm = times[1:] or times
         print(f"rank {rank}/{world}: {len(mine)} of {len(scenes)} scenes, {views_done} reference views, "
               f"{1.0 / (sum(warm) / len(warm)):.1f} ref-views/s (model time), clouds under {args.plydir}")
+
+
+DEDUP_AND_MESH = ("--fusion-dedup does not go with --mesh: the TSDF volume averages EVERY observation of a surface, and suppression keeps "
+                  "one view's sample of it and drops the rest; fuse the cloud with --fusion-dedup in one run and mesh in another")
+
+
+def mesh_fusion_options(args):
+    """the fusion method for the mesh path (tsdf_mesh.mesh_scan, mesh_scan_tanks): the method and its parameters, never the dedup"""
+    return {k: args.fusion_options[k] for k in ("method", "dynamic")} if args.fusion_options else {}
 
 
 def score_scan(args, scan, device):
@@ -299,6 +319,8 @@ def main(argv=None):
     ap.add_argument("--num_consistency", type=int, default=3)
     ap.add_argument("--img_dist_thres", type=float, default=0.5)
     ap.add_argument("--depth_thres", type=float, default=0.01)
+    from .fusion import add_fusion_arguments, fusion_options
+    add_fusion_arguments(ap)
     ap.add_argument("--outdir", required=True)
     ap.add_argument("--scans", type=int, default=2)
     ap.add_argument("--ref-views", type=int, default=2, help="reference views per scan")
@@ -322,6 +344,11 @@ def main(argv=None):
         tanks_scenes(args)                                              # argument errors end here, before any rank starts or the network is built
     if args.dtu_gt and not args.filter:
         raise SystemExit("eval_driver: --dtu-gt scores the clouds of --filter; give both")
+    args.fusion_options = fusion_options(args, "eval_driver")
+    if args.fusion_options and not tanks and not args.filter:
+        raise SystemExit("eval_driver: --fusion, --fusion-dedup and --dyn-* set up the fusion step; give --filter")
+    if args.fusion_options and args.fusion_options["dedup"] and args.mesh:
+        raise SystemExit("eval_driver: " + DEDUP_AND_MESH)
     if args.mesh and not tanks and (not args.filter or not args.testpath):
         raise SystemExit("eval_driver: --mesh meshes the depth maps --filter fuses (real-layout DTU data: --testpath, --filter); give both")
     nproc = args.gpus * args.procs_per_gpu

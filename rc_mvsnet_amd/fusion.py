@@ -74,6 +74,195 @@ def fuse_view(depth_all, ref_idx, src_idx, conf, img, mats, prob_threshold, num_
     return out
 
 
+METHODS = ("reference", "dynamic")
+DYN_DEFAULTS = {"level_lo": 2, "level_hi": None, "dist_base": 0.25, "rel_base": 1.0 / 1300.0}      # the common published form of the dynamic check
+
+
+def dynamic_params(dynamic, n_src):
+    """The four parameters of the dynamic check for a view with ``n_src`` sources: DYN_DEFAULTS overridden by ``dynamic`` (a dict,
+    unknown keys refused).  level_hi None means "as many levels as there are sources", but never fewer than level_lo: with one
+    source and level_lo = 2 the only level is 2, which one source cannot reach, so nothing is consistent."""
+    p = dict(DYN_DEFAULTS)
+    for k, v in (dynamic or {}).items():
+        if k not in p:
+            raise _lib.RcmvsError(f"dynamic fusion: unknown parameter {k!r} (known: {', '.join(DYN_DEFAULTS)})")
+        p[k] = v
+    p["level_lo"] = int(p["level_lo"])
+    p["level_hi"] = max(int(n_src), p["level_lo"]) if p["level_hi"] is None else int(p["level_hi"])
+    p["dist_base"], p["rel_base"] = float(p["dist_base"]), float(p["rel_base"])
+    return p
+
+
+def check_levels(level_lo, level_hi, what="fuse_view_dynamic"):
+    if not 1 <= level_lo <= level_hi <= MAX_SRC:
+        raise _lib.RcmvsError(f"{what}: levels {level_lo}..{level_hi} (1 <= lo <= hi <= {MAX_SRC})")
+
+
+def fuse_view_dynamic(depth_all, ref_idx, src_idx, conf, img, mats, prob_threshold, level_lo=2, level_hi=None, dist_base=0.25,
+                      rel_base=1.0 / 1300.0, used=None, debug=False):
+    """fuse_view with the dynamic consistency check and, with ``used``, one point per surface (csrc/fusion_dyn.h has the rule).
+    Source i passes level n when dist_i < n * dist_base (fp64, pixels) and rel_i < n * rel_base (fp32); a pixel's level is the
+    smallest n in [level_lo, level_hi] that n sources pass, 0 for none, and geo = level != 0.  level_hi None: max(N, level_lo).
+    used: (n_views,H,W) uint8 on the device, zero-filled by the caller ONCE PER SCAN, or None.  A kept pixel marks the pixel it
+    falls on in every source that passes level_hi; a pixel whose own byte is already set is ``claimed`` and dropped.  Within one
+    call nothing depends on the schedule, but the result DOES depend on the order in which the reference views of a scan are
+    passed: that order is pair.txt's, and every launch goes on the one current stream.
+    Returns dict: masks (4,H,W) uint8 [photo, geo, final, claimed], level (H,W) uint8, depth_avg (H,W), xyz (H,W,3), rgb (H,W,3)
+    uint8 or None, and with debug=True depth_reprojected (N,H,W) (0 where the source fails level_hi), src_level (N,H,W) uint8,
+    xy_src (N,H,W,2)."""
+    N = len(src_idx)
+    if not 1 <= N <= MAX_SRC:
+        raise _lib.RcmvsError(f"fuse_view_dynamic: {N} source views (1..{MAX_SRC})")
+    level_lo = int(level_lo)
+    level_hi = max(N, level_lo) if level_hi is None else int(level_hi)
+    check_levels(level_lo, level_hi)
+    n_views, H, W = depth_all.shape
+    if not all(0 <= int(i) < n_views for i in [ref_idx] + list(src_idx)):
+        raise _lib.RcmvsError(f"fuse_view_dynamic: view index outside the {n_views} views of depth_all")
+    if mats.numel() != REF_MATS + SRC_MATS * N:
+        raise _lib.RcmvsError(f"fuse_view_dynamic: mats has {mats.numel()} values, expected {REF_MATS + SRC_MATS * N}")
+    if used is not None and tuple(used.shape) != (n_views, H, W):
+        raise _lib.RcmvsError(f"fuse_view_dynamic: used is {tuple(used.shape)}, expected {(n_views, H, W)}")
+    dev = depth_all.device
+    masks = torch.empty((4, H, W), device=dev, dtype=torch.uint8)
+    level = torch.empty((H, W), device=dev, dtype=torch.uint8)
+    depth_avg = torch.empty((H, W), device=dev, dtype=torch.float32)
+    xyz = torch.empty((H, W, 3), device=dev, dtype=torch.float32)
+    rgb = torch.empty((H, W, 3), device=dev, dtype=torch.uint8) if img is not None else None
+    dbg_d = torch.empty((N, H, W), device=dev, dtype=torch.float32) if debug else None
+    dbg_l = torch.empty((N, H, W), device=dev, dtype=torch.uint8) if debug else None
+    dbg_xy = torch.empty((N, H, W, 2), device=dev, dtype=torch.float32) if debug else None
+    idx = (ctypes.c_int * N)(*[int(i) for i in src_idx])
+    _lib.call("rcmvs_fuse_view_dyn",
+        _chk(depth_all, "depth_all"), int(n_views), int(ref_idx), ctypes.cast(idx, ctypes.c_void_p), _chk(conf, "conf"), _ptr(img, "img", torch.float32),
+        _chk(mats, "mats", torch.float64), ctypes.c_float(prob_threshold), level_lo, level_hi, ctypes.c_double(dist_base), ctypes.c_float(rel_base),
+        _ptr(used, "used", torch.uint8), _chk(masks, "masks", torch.uint8), _chk(level, "level", torch.uint8), _chk(depth_avg, "depth_avg"),
+        _chk(xyz, "xyz"), _ptr(rgb, "rgb", torch.uint8), _ptr(dbg_d, "dbg_depth", torch.float32), _ptr(dbg_l, "dbg_level", torch.uint8),
+        _ptr(dbg_xy, "dbg_xy", torch.float32), N, H, W, _stream())
+    out = {"masks": masks, "level": level, "depth_avg": depth_avg, "xyz": xyz, "rgb": rgb}
+    if debug:
+        out.update({"depth_reprojected": dbg_d, "src_level": dbg_l, "xy_src": dbg_xy})
+    return out
+
+
+def reference_bases(num_consistent, img_dist_thresh, depth_thresh):
+    """(dist_base, rel_base) at which level k = num_consistent of the dynamic check has EXACTLY the fixed filter's thresholds:
+    (double)k * dist_base == img_dist_thresh and (float)k * rel_base == float32(depth_thresh) in every bit, so that
+    level_lo = level_hi = k keeps the pixels rcmvs_fuse_view keeps and averages the same depths.  t / k times k does not always
+    round back to t; the few neighbours of t / k are tried, and where none gives t the combination is refused."""
+    k = int(num_consistent)
+    if not 1 <= k <= MAX_SRC:
+        raise _lib.RcmvsError(f"dedup with method='reference' runs the fixed check as level {k} of the dynamic kernel, which has levels 1..{MAX_SRC}")
+
+    def base(t, ftype):
+        t, kk = ftype(t), ftype(k)
+        b = t / kk
+        cands = [b]
+        for towards in (ftype(-np.inf), ftype(np.inf)):
+            c = b
+            for _ in range(3):
+                c = np.nextafter(c, towards)
+                cands.append(c)
+        for c in cands:
+            if kk * c == t:
+                return float(c)
+        raise _lib.RcmvsError(f"dedup with method='reference': no {ftype.__name__} base b has {k} * b == {t!r} exactly, so the dynamic kernel "
+                              "cannot restate the fixed thresholds bit for bit; use method='dynamic' or drop dedup")
+    return base(img_dist_thresh, np.float64), base(depth_thresh, np.float32)
+
+
+def add_fusion_arguments(ap, dedup=True):
+    """The fusion options of the drivers (eval_driver, tsdf_mesh): every default is None / False, so that fusion_options can tell
+    "not given" from a value."""
+    ap.add_argument("--fusion", choices=METHODS, default=None,
+                    help="the consistency check of the fusion filter: reference (default: fixed thresholds, --num_consistency views) or dynamic "
+                         "(n views within n times the base thresholds, for some n of --dyn-levels; no per-scene tuning)")
+    if dedup:
+        ap.add_argument("--fusion-dedup", action="store_true",
+                        help="one point per surface: a fused point marks the source pixels it accounts for and later reference views skip them")
+    ap.add_argument("--dyn-levels", type=int, nargs=2, default=None, metavar=("LO", "HI"),
+                    help=f"--fusion dynamic: the levels tried (default 2 and the number of source views; at most {MAX_SRC})")
+    ap.add_argument("--dyn-dist-base", type=float, default=None, help="--fusion dynamic: reprojection distance of level 1 in pixels (default 0.25)")
+    ap.add_argument("--dyn-rel-base", type=float, default=None, help="--fusion dynamic: relative depth difference of level 1 (default 1/1300)")
+
+
+def fusion_options(args, who):
+    """The parsed fusion options -> the keywords filter_depth / filter_depth_tanks take for them ({} when none was given, so that a run
+    without them calls what it called before); argument errors end the run with one line."""
+    dyn = {k: v for k, v in (("levels", args.dyn_levels), ("dist_base", args.dyn_dist_base), ("rel_base", args.dyn_rel_base)) if v is not None}
+    dedup = bool(getattr(args, "fusion_dedup", False))
+    if args.fusion is None and not dedup and not dyn:
+        return {}
+    method = args.fusion or "reference"
+    if dyn and method != "dynamic":
+        raise SystemExit(f"{who}: --dyn-levels, --dyn-dist-base and --dyn-rel-base belong to --fusion dynamic")
+    dynamic = None
+    if method == "dynamic":
+        dynamic = {k: dyn[k] for k in ("dist_base", "rel_base") if k in dyn}
+        if "levels" in dyn:
+            lo, hi = dyn["levels"]
+            if not 1 <= lo <= hi <= MAX_SRC:
+                raise SystemExit(f"{who}: --dyn-levels {lo} {hi}: 1 <= LO <= HI <= {MAX_SRC}")
+            dynamic.update({"level_lo": lo, "level_hi": hi})
+    return {"method": method, "dynamic": dynamic, "dedup": dedup}
+
+
+def fusion_summary(options, stats, fixed=None):
+    """what a driver's summary reports as "fusion": method, levels, bases, dedup, points and claimed.  fixed = (num_consistent,
+    img_dist_thresh, depth_thresh) of the reference method."""
+    if options["method"] == "dynamic":
+        p = dict(DYN_DEFAULTS, **(options["dynamic"] or {}))
+        levels, dist_base, rel_base = [p["level_lo"], p["level_hi"]], p["dist_base"], p["rel_base"]      # level_hi None: the number of source views
+    else:
+        levels = [int(fixed[0])] * 2
+        k = int(fixed[0])                                           # without dedup the fixed thresholds are used as they are: bases for the record
+        dist_base, rel_base = reference_bases(*fixed) if options["dedup"] else ((fixed[1] / k, fixed[2] / k) if k else (None, None))
+    return {"method": options["method"], "levels": levels, "dist_base": dist_base, "rel_base": rel_base, "dedup": bool(options["dedup"]),
+            "points": int(stats.get("kept", 0)), "claimed": int(stats.get("claimed", 0))}
+
+
+def _fuse_dyn(depth_all, ref_slot, src_slots, conf, img, mats, prob, method, dynamic, fixed, used):
+    """one reference view through rcmvs_fuse_view_dyn for filter_depth / filter_depth_tanks: -> (result dict, parameters used)"""
+    if method == "dynamic":
+        p = dynamic_params(dynamic, len(src_slots))
+    else:                                                           # the fixed check restated as one level (dedup=True only)
+        k, dist_t, depth_t = fixed
+        db, rb = reference_bases(k, dist_t, depth_t)
+        p = {"level_lo": int(k), "level_hi": int(k), "dist_base": db, "rel_base": rb}
+    check_levels(p["level_lo"], p["level_hi"], "filter_depth")
+    r = fuse_view_dynamic(depth_all, ref_slot, src_slots, conf, img, mats, prob, p["level_lo"], p["level_hi"], p["dist_base"], p["rel_base"], used=used)
+    return r, p
+
+
+def _check_method(method, dynamic, dedup):
+    if method not in METHODS:
+        raise _lib.RcmvsError(f"fusion method {method!r} (one of {', '.join(METHODS)})")
+    if dynamic is not None and method != "dynamic":
+        raise _lib.RcmvsError("the `dynamic` parameters apply to method='dynamic' only")
+    return method == "reference" and not dedup                      # True: today's path, rcmvs_fuse_view
+
+
+def _compact_counted(masks, xyz, rgb):
+    """compact_points on masks[2] plus the number of claimed pixels (masks[3]), both fetched in the view's one host read"""
+    mask = masks[2]
+    n = mask.numel()
+    dev = mask.device
+    out_xyz = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    out_rgb = torch.empty((n, 3), device=dev, dtype=torch.uint8)
+    offsets = torch.empty((n + 255) // 256 + 1, device=dev, dtype=torch.int32)
+    _lib.call("rcmvs_compact_points", _chk(mask, "mask", torch.uint8), _chk(xyz, "xyz"), _chk(rgb, "rgb", torch.uint8),
+              _chk(out_xyz, "out_xyz"), _chk(out_rgb, "out_rgb", torch.uint8), _chk(offsets, "offsets", torch.int32), n, _stream())
+    kept, claimed = torch.stack([offsets[-1].to(torch.int64), masks[3].sum(dtype=torch.int64)]).tolist()
+    return out_xyz[:kept], out_rgb[:kept], kept, claimed
+
+
+def _stats_add(stats, ref, kept, claimed):
+    if stats is not None:
+        stats.setdefault("views", []).append({"ref": int(ref), "kept": int(kept), "claimed": int(claimed)})
+        stats["kept"] = stats.get("kept", 0) + int(kept)
+        stats["claimed"] = stats.get("claimed", 0) + int(claimed)
+
+
 def compact_points(mask, xyz, rgb=None):
     """numpy's ``xyz[mask]`` / ``rgb[mask]`` on the device, row-major order kept.  mask (H,W) uint8 -> (n,3) fp32[, (n,3) uint8]."""
     n = mask.numel()
@@ -127,8 +316,15 @@ def stage_colour(img, num_stage, shape):
 
 
 def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, prob_threshold, num_consistent, img_dist_thresh, depth_thresh,
-                 num_stage=3, device="cuda:0", save_masks=True, verbose=True):
-    """eval_rcmvsnet_dtu.py:341-446: fuse one scan into ``plyfilename``; returns (xyz (n,3) fp32, rgb (n,3) uint8)."""
+                 num_stage=3, device="cuda:0", save_masks=True, verbose=True, method="reference", dynamic=None, dedup=False, stats=None):
+    """eval_rcmvsnet_dtu.py:341-446: fuse one scan into ``plyfilename``; returns (xyz (n,3) fp32, rgb (n,3) uint8).
+    method="reference" without dedup is the reference's filter (rcmvs_fuse_view), to the byte.  method="dynamic": the dynamic
+    consistency check (fuse_view_dynamic) with the parameters of ``dynamic`` (a dict over DYN_DEFAULTS); prob_threshold stays the
+    caller's, num_consistent and the two fixed thresholds are not used.  dedup=True: one point per surface, with either method (for
+    "reference" the fixed check runs as one level of the dynamic kernel, see reference_bases); the cloud then depends on the order
+    of pair.txt's reference views, which is the order of the launches, and a fourth mask image <view>_claimed.png is written.
+    stats: a dict that receives "views" = [{"ref", "kept", "claimed"}], "kept" and "claimed"."""
+    plain = _check_method(method, dynamic, dedup)
     dev = torch.device(device)
     pairs = scan_io.read_pair_file(os.path.join(pair_folder, "pair.txt"))
     views = sorted({v for ref, srcs in pairs for v in [ref] + list(srcs)})
@@ -137,6 +333,8 @@ def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, prob_thresho
     depth_all = torch.from_numpy(np.stack([read_pfm(os.path.join(out_folder, "depth_est/{:0>8}.pfm".format(v)))[0] for v in views])).to(dev)
     if save_masks:
         os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
+    used = torch.zeros(depth_all.shape, device=dev, dtype=torch.uint8) if dedup else None      # zero-filled once per scan
+    kinds = ("photo", "geo", "final") + (("claimed",) if dedup else ())
     pts, cols = [], []
     for ref, srcs in pairs:
         if len(srcs) > MAX_SRC:
@@ -145,14 +343,21 @@ def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, prob_thresho
         img = scan_io.read_img(os.path.join(scan_folder, "images/{:0>8}.jpg".format(ref)))
         img = torch.from_numpy(stage_colour(img, num_stage, conf.shape)).to(dev)
         mats = torch.from_numpy(fusion_matrices(cams[ref][0], cams[ref][1], [cams[s][0] for s in srcs], [cams[s][1] for s in srcs])).to(dev)
-        r = fuse_view(depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, prob_threshold, num_consistent, img_dist_thresh, depth_thresh)
-        xyz, rgb = compact_points(r["masks"][2], r["xyz"], r["rgb"])
+        if plain:
+            r = fuse_view(depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, prob_threshold, num_consistent, img_dist_thresh, depth_thresh)
+            xyz, rgb = compact_points(r["masks"][2], r["xyz"], r["rgb"])
+            _stats_add(stats, ref, len(xyz), 0)
+        else:
+            r, _ = _fuse_dyn(depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, prob_threshold, method, dynamic,
+                             (num_consistent, img_dist_thresh, depth_thresh), used)
+            xyz, rgb, kept, claimed = _compact_counted(r["masks"], r["xyz"], r["rgb"])
+            _stats_add(stats, ref, kept, claimed)
         pts.append(xyz.cpu().numpy())
         cols.append(rgb.cpu().numpy())
         if save_masks or verbose:
             m = r["masks"].cpu().numpy().astype(bool)
             if save_masks:
-                for k, kind in enumerate(("photo", "geo", "final")):
+                for k, kind in enumerate(kinds):
                     scan_io.save_mask(os.path.join(out_folder, "mask/{:0>8}_{}.png".format(ref, kind)), m[k])
             if verbose:
                 print("processing {}, ref-view{:0>2}, photo/geo/final-mask:{}/{}/{}".format(scan_folder, ref, m[0].mean(), m[1].mean(), m[2].mean()))
@@ -202,14 +407,16 @@ def _resident(maps, view, dev, what):
 
 def filter_depth_tanks(scan_folder, out_folder, plyfilename, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes,
                        geo_mask_thres, n_views=None, scan="", device="cuda:0", save_masks=True, verbose=True, depth_maps=None,
-                       conf_maps=None):
+                       conf_maps=None, method="reference", dynamic=None, dedup=False, stats=None):
     """eval_rcmvsnet_tanks.py:269-380, the Tanks-and-Temples form of filter_depth: pair.txt, cams_1/ and images/ live in
     ``scan_folder`` at the ORIGINAL image size ``image_sizes`` = (w, h); the depth maps under ``out_folder`` have the network
     size ``img_wh`` = (w, h), so the intrinsics' first two rows are rescaled and the colour image is resized (cv2.resize's
     rule, on the device).  Same kernels as filter_depth.  depth_maps / conf_maps: optional {view: (H,W) fp32 tensor on ``device``},
     the network's outputs still in HBM; where a view is present its PFM file is not read (PFM holds fp32 losslessly, so the
-    cloud is the same to the byte).  Returns (xyz (n,3) fp32, rgb (n,3) uint8)."""
+    cloud is the same to the byte).  method / dynamic / dedup / stats: as filter_depth's; with method="dynamic" photo_thres stays the
+    scene's and geo_mask_thres, geo_pixel_thres and geo_depth_thres are not used.  Returns (xyz (n,3) fp32, rgb (n,3) uint8)."""
     from .mvs_dataset import prepare_image
+    plain = _check_method(method, dynamic, dedup)
     dev = torch.device(device)
     if dev.type == "cuda" and dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -235,6 +442,8 @@ def filter_depth_tanks(scan_folder, out_folder, plyfilename, geo_pixel_thres, ge
         raise _lib.RcmvsError(f"filter_depth_tanks: depth maps are {tuple(depth_all.shape[1:])}, img_wh says {(img_wh[1], img_wh[0])}")
     if save_masks:
         os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
+    used = torch.zeros(depth_all.shape, device=dev, dtype=torch.uint8) if dedup else None      # zero-filled once per scan
+    kinds = ("photo", "geo", "final") + (("claimed",) if dedup else ())
     pts, cols = [], []
     for ref, srcs in pairs:
         if len(srcs) > MAX_SRC:
@@ -245,14 +454,21 @@ def filter_depth_tanks(scan_folder, out_folder, plyfilename, geo_pixel_thres, ge
         raw = np.array(Image.open(os.path.join(scan_folder, "images/{:0>8}.jpg".format(ref))), dtype=np.uint8)
         img = prepare_image(raw, (img_wh[1], img_wh[0]), dev, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)).permute(1, 2, 0).contiguous()
         mats = torch.from_numpy(fusion_matrices(cams[ref][0], cams[ref][1], [cams[s][0] for s in srcs], [cams[s][1] for s in srcs])).to(dev)
-        r = fuse_view(depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, photo_thres, geo_mask_thres, geo_pixel_thres, geo_depth_thres)
-        xyz, rgb = compact_points(r["masks"][2], r["xyz"], r["rgb"])
+        if plain:
+            r = fuse_view(depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, photo_thres, geo_mask_thres, geo_pixel_thres, geo_depth_thres)
+            xyz, rgb = compact_points(r["masks"][2], r["xyz"], r["rgb"])
+            _stats_add(stats, ref, len(xyz), 0)
+        else:
+            r, _ = _fuse_dyn(depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, photo_thres, method, dynamic,
+                             (geo_mask_thres, geo_pixel_thres, geo_depth_thres), used)
+            xyz, rgb, kept, claimed = _compact_counted(r["masks"], r["xyz"], r["rgb"])
+            _stats_add(stats, ref, kept, claimed)
         pts.append(xyz.cpu().numpy())
         cols.append(rgb.cpu().numpy())
         if save_masks or verbose:
             m = r["masks"].cpu().numpy().astype(bool)
             if save_masks:
-                for k, kind in enumerate(("photo", "geo", "final")):
+                for k, kind in enumerate(kinds):
                     scan_io.save_mask(os.path.join(out_folder, "mask/{:0>8}_{}.png".format(ref, kind)), m[k])
             if verbose:
                 print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(

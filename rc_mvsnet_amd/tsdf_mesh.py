@@ -331,11 +331,39 @@ def _add_view(r, cam, depths, colours, rows, lo, hi):
     return lo, hi
 
 
+def _fuse(method, dynamic, depth_all, ref_slot, src_slots, conf, img, mats, prob, num_consistent, dist_thresh, depth_thresh, stats):
+    """one reference view for the mesh path: fusion.fuse_view, or with method="dynamic" fusion.fuse_view_dynamic.  Never with
+    duplicate suppression: the volume averages every observation of a surface."""
+    if fusion._check_method(method or "reference", dynamic, False):
+        r = fusion.fuse_view(depth_all, ref_slot, src_slots, conf, img, mats, prob, num_consistent, dist_thresh, depth_thresh)
+    else:
+        r, _ = fusion._fuse_dyn(depth_all, ref_slot, src_slots, conf, img, mats, prob, method, dynamic, None, None)
+    if stats is not None:
+        stats["kept"] = stats.get("kept", 0) + int((r["masks"][2] != 0).sum())
+    return r
+
+
+def _fusion_argument(method, dynamic):
+    """-> the keywords filtered_views takes for a fusion method that was asked for, and the dict its counts go to; nothing when none was"""
+    if method is None and dynamic is None:
+        return {}, None
+    stats = {}
+    return {"method": method or "reference", "dynamic": dynamic, "stats": stats}, stats
+
+
+def _with_fusion(summary, method, dynamic, stats, fixed):
+    if stats is not None:
+        summary["fusion"] = fusion.fusion_summary({"method": method or "reference", "dynamic": dynamic, "dedup": False}, stats, fixed)
+    return summary
+
+
 def filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage=3,
-                   device="cuda:0"):
+                   device="cuda:0", method="reference", dynamic=None, stats=None):
     """fusion.fuse_view per reference view of pair.txt, as filter_depth runs it -> dict: depth (V,H,W) fp32 = depth_avg where the
     final mask holds and 0 elsewhere, rgb (V,H,W,3) uint8, both on the device; cams (V,16) float64; lo, hi: the bounding box of
-    the surviving points (float64, None when no point survives); ids: the V reference views' numbers in pair.txt's order."""
+    the surviving points (float64, None when no point survives); ids: the V reference views' numbers in pair.txt's order.
+    method / dynamic: filter_depth's; there is no dedup here, the volume wants every observation.  stats: a dict that receives the
+    number of pixels kept as "kept" (one more host read per view)."""
     dev = torch.device(device)
     pairs = scan_io.read_pair_file(os.path.join(pair_folder, "pair.txt"))
     views = sorted({v for ref, srcs in pairs for v in [ref] + list(srcs)})
@@ -350,15 +378,15 @@ def filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_con
         img = scan_io.read_img(os.path.join(scan_folder, "images/{:0>8}.jpg".format(ref)))
         img = torch.from_numpy(fusion.stage_colour(img, num_stage, conf.shape)).to(dev)
         mats = torch.from_numpy(fusion.fusion_matrices(cams[ref][0], cams[ref][1], [cams[s][0] for s in srcs], [cams[s][1] for s in srcs])).to(dev)
-        r = fusion.fuse_view(depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, prob_threshold, num_consistent, img_dist_thresh,
-                             depth_thresh)
+        r = _fuse(method, dynamic, depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, prob_threshold, num_consistent, img_dist_thresh,
+                  depth_thresh, stats)
         lo, hi = _add_view(r, cams[ref], depths, colours, rows, lo, hi)
     return {"depth": torch.stack(depths).contiguous(), "rgb": torch.stack(colours).contiguous(), "cams": np.stack(rows), "lo": lo, "hi": hi,
             "ids": [int(ref) for ref, _ in pairs]}
 
 
 def filtered_views_tanks(scan_folder, out_folder, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes, geo_mask_thres,
-                         device="cuda:0", depth_maps=None, conf_maps=None):
+                         device="cuda:0", depth_maps=None, conf_maps=None, method="reference", dynamic=None, stats=None):
     """filtered_views for a Tanks-and-Temples scene, as fusion.filter_depth_tanks runs the filter: cams_1/ with the intrinsics
     rescaled to ``img_wh``, the image resized by prepare_image, depth_maps / conf_maps optionally still on the device."""
     from PIL import Image
@@ -394,8 +422,8 @@ def filtered_views_tanks(scan_folder, out_folder, geo_pixel_thres, geo_depth_thr
         raw = np.array(Image.open(os.path.join(scan_folder, "images/{:0>8}.jpg".format(ref))), dtype=np.uint8)
         img = prepare_image(raw, (img_wh[1], img_wh[0]), dev, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)).permute(1, 2, 0).contiguous()
         mats = torch.from_numpy(fusion.fusion_matrices(cams[ref][0], cams[ref][1], [cams[s][0] for s in srcs], [cams[s][1] for s in srcs])).to(dev)
-        r = fusion.fuse_view(depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, photo_thres, geo_mask_thres, geo_pixel_thres,
-                             geo_depth_thres)
+        r = _fuse(method, dynamic, depth_all, slot[ref], [slot[s] for s in srcs], conf, img, mats, photo_thres, geo_mask_thres, geo_pixel_thres,
+                  geo_depth_thres, stats)
         lo, hi = _add_view(r, cams[ref], depths, colours, rows, lo, hi)
     return {"depth": torch.stack(depths).contiguous(), "rgb": torch.stack(colours).contiguous(), "cams": np.stack(rows), "lo": lo, "hi": hi,
             "ids": [int(ref) for ref, _ in pairs]}
@@ -404,23 +432,26 @@ def filtered_views_tanks(scan_folder, out_folder, geo_pixel_thres, geo_depth_thr
 def mesh_scan_tanks(scan_folder, out_folder, meshfilename, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes, geo_mask_thres,
                     n_views=None, scan="", device="cuda:0", depth_maps=None, conf_maps=None, voxel=None, resolution=1024, trunc_voxels=3.0,
                     min_weight=1, bounds=None, min_faces=0, min_fraction=0.0, keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0,
-                    render_dir=None, normals=None, texture=False, texture_size=None, simplify_faces=0, simplify_ratio=0.0, simplify_max_error=None):
+                    render_dir=None, normals=None, texture=False, texture_size=None, simplify_faces=0, simplify_ratio=0.0, simplify_max_error=None,
+                    method=None, dynamic=None):
     """The mesh counterpart of fusion.filter_depth_tanks, with its arguments: the scene's filtered ``depth_avg`` maps integrated into
     a SparseTsdfVolume (always sparse: these are the scenes a dense box does not fit) and meshed into ``meshfilename``.  Where no
     point survives the filter and no bounds are given there is nothing to put a grid round: the PLY is written empty, as
-    filter_depth_tanks writes an empty cloud, and the summary says so."""
+    filter_depth_tanks writes an empty cloud, and the summary says so.  method / dynamic: as mesh_scan's."""
+    fuse_kw, fstats = _fusion_argument(method, dynamic)
+    fixed = (geo_mask_thres, geo_pixel_thres, geo_depth_thres)
     views = filtered_views_tanks(scan_folder, out_folder, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes, geo_mask_thres,
-                                 device, depth_maps, conf_maps)
+                                 device, depth_maps, conf_maps, **fuse_kw)
     if bounds is None and views["lo"] is None:
         os.makedirs(os.path.dirname(os.path.abspath(meshfilename)), exist_ok=True)
         with open(meshfilename, "wb") as f:
             f.write(mesh_ply_bytes(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)))
-        return {"mesh": meshfilename, "views": int(views["depth"].shape[0]), "vertices": 0, "faces": 0, "active_blocks": 0, "allocated_voxels": 0,
-                "skipped_pixels": 0, "empty": "no point survives the filter"}
-    return _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, True, device,
+        return _with_fusion({"mesh": meshfilename, "views": int(views["depth"].shape[0]), "vertices": 0, "faces": 0, "active_blocks": 0, "allocated_voxels": 0,
+                             "skipped_pixels": 0, "empty": "no point survives the filter"}, method, dynamic, fstats, fixed)
+    return _with_fusion(_mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, True, device,
                        mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth, fill_holes), **_decimate_argument(decimate_cell, decimate_voxels),
                        **_simplify_argument(simplify_faces, simplify_ratio, simplify_max_error),
-                       **_render_argument(render_dir), **_normals_argument(normals), **_texture_argument(texture, texture_size))
+                       **_render_argument(render_dir), **_normals_argument(normals), **_texture_argument(texture, texture_size)), method, dynamic, fstats, fixed)
 
 
 def _decimate_argument(cell, voxels):
@@ -572,8 +603,10 @@ def _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight
 def mesh_scan(pair_folder, scan_folder, out_folder, meshfilename, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage=3,
               voxel=None, resolution=256, trunc_voxels=3.0, min_weight=1, bounds=None, device="cuda:0", sparse=False, min_faces=0, min_fraction=0.0,
               keep_largest=0, smooth=0, decimate_cell=0.0, decimate_voxels=0.0, fill_holes=0, render_dir=None, normals=None, texture=False,
-              texture_size=None, simplify_faces=0, simplify_ratio=0.0, simplify_max_error=None):
-    """Mesh one scan laid out as fusion.filter_depth reads it into ``meshfilename``.  bounds: (xmin, ymin, zmin, xmax, ymax, zmax),
+              texture_size=None, simplify_faces=0, simplify_ratio=0.0, simplify_max_error=None, method=None, dynamic=None):
+    """Mesh one scan laid out as fusion.filter_depth reads it into ``meshfilename``.  method ("reference" or "dynamic") / dynamic: the
+    consistency check of the filter, as fusion.filter_depth takes them; either given, the summary gains "fusion".  There is no dedup
+    here: the volume averages every observation of a surface, and duplicate suppression would keep one and drop the rest.  bounds: (xmin, ymin, zmin, xmax, ymax, zmax),
     default the bounding box of the points that survive the filter, padded by the truncation distance.  sparse: a SparseTsdfVolume
     planned by plan_sparse_grid (resolution None: 1024); the summary then also reports bdims, active_blocks, allocated_voxels and
     skipped_pixels.  min_faces, min_fraction, keep_largest, smooth, fill_holes: any of them given, mesh_clean.clean_mesh runs on the
@@ -587,13 +620,15 @@ def mesh_scan(pair_folder, scan_folder, out_folder, meshfilename, prob_threshold
     render gains the smooth shade and the normal image.  texture: mesh_texture.texture runs last, on the mesh that is written, from the
     views' images and cameras (texture_size: the atlas's largest side, default 8192); the PLY's faces gain texcoords, the atlas is written
     next to it as <name>.png, the summary gains "texture", and a render gains the textured views.  Returns the summary dict."""
-    views = filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage, device)
+    fuse_kw, fstats = _fusion_argument(method, dynamic)
+    views = filtered_views(pair_folder, scan_folder, out_folder, prob_threshold, num_consistent, img_dist_thresh, depth_thresh, num_stage, device, **fuse_kw)
     if resolution is None:
         resolution = 1024 if sparse else 256
-    return _mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, bool(sparse), device,
+    return _with_fusion(_mesh_views(views, meshfilename, voxel, resolution, trunc_voxels, min_weight, bounds, bool(sparse), device,
                        mesh_clean.clean_options(min_faces, min_fraction, keep_largest, smooth, fill_holes), **_decimate_argument(decimate_cell, decimate_voxels),
                        **_simplify_argument(simplify_faces, simplify_ratio, simplify_max_error),
-                       **_render_argument(render_dir), **_normals_argument(normals), **_texture_argument(texture, texture_size))
+                       **_render_argument(render_dir), **_normals_argument(normals), **_texture_argument(texture, texture_size)),
+                        method, dynamic, fstats, (num_consistent, img_dist_thresh, depth_thresh))
 
 
 def main(argv=None):
@@ -633,14 +668,21 @@ def main(argv=None):
                                                            "PLY, the atlas next to it as <name>.png; with --render also <view>_tex.png")
     ap.add_argument("--texture-size", type=int, default=None, metavar="N", help="the atlas's largest side (default 8192, at most 16384)")
     ap.add_argument("--device", default="cuda:0")
+    fusion.add_fusion_arguments(ap, dedup=False)
+    ap.add_argument("--fusion-dedup", action="store_true", help="refused: the volume wants every observation (fuse the cloud with eval_driver --fusion-dedup)")
     a = ap.parse_args(argv)
+    if a.fusion_dedup:
+        raise SystemExit("tsdf_mesh: --fusion-dedup is for point clouds: the TSDF volume averages EVERY observation of a surface, and suppression "
+                         "keeps one view's sample of it and drops the rest")
+    fopt = fusion.fusion_options(a, "tsdf_mesh")
     summary = mesh_scan(a.pair_folder, a.scan_folder, a.out_folder, a.mesh, a.prob_thres, a.num_consistency, a.img_dist_thres, a.depth_thres,
                         num_stage=a.num_stage, voxel=a.voxel, resolution=a.resolution, trunc_voxels=a.trunc_voxels, min_weight=a.min_weight,
                         bounds=a.bounds, device=a.device, sparse=a.sparse, min_faces=a.min_faces, min_fraction=a.min_fraction,
                         keep_largest=a.keep_largest, smooth=a.smooth, decimate_cell=a.decimate_cell, decimate_voxels=a.decimate_voxels,
                         fill_holes=a.fill_holes, render_dir=a.render, normals=a.normals, **({"texture": True, "texture_size": a.texture_size} if a.texture else {}),
                         **({"simplify_faces": a.simplify_faces, "simplify_ratio": a.simplify_ratio, "simplify_max_error": a.simplify_max_error}
-                           if (a.simplify_faces or a.simplify_ratio or a.simplify_max_error is not None) else {}))
+                           if (a.simplify_faces or a.simplify_ratio or a.simplify_max_error is not None) else {}),
+                        **({"method": fopt["method"], "dynamic": fopt["dynamic"]} if fopt else {}))
     print(json.dumps(summary))
     return summary
 
