@@ -271,6 +271,13 @@ def read_ply_mesh_normals(path):
     return _read_ply_mesh(path, True, True)
 
 
+def read_ply_cloud_normals(path):
+    """A point cloud that fusion.ply_bytes wrote -> (xyz (n,3) float32, rgb (n,3) uint8 or None, normals (n,3) float32 or None, with
+    their bits as stored): read_ply_mesh_normals without the faces."""
+    verts, _, rgb, nrm = _read_ply_mesh(path, True, True)
+    return verts, rgb, nrm
+
+
 def _read_ply_mesh(path, colours, normals=False):
     """the reader behind read_ply_mesh, read_ply_mesh_rgb and read_ply_mesh_normals -> (verts, faces, rgb or None), with normals
     (verts, faces, rgb or None, normals or None); colours False: rgb is not looked for"""

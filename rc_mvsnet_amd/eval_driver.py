@@ -121,10 +121,14 @@ def run_scans(model, args, device, rank, world):
             fstats = {}
             fusion.filter_depth(os.path.join(args.testpath, scan), folder, folder, os.path.join(args.outdir, scan + ".ply"),
                                 args.prob_thres, args.num_consistency, args.img_dist_thres, args.depth_thres,
-                                num_stage=nstage, device=str(device), **(dict(args.fusion_options, stats=fstats) if args.fusion_options else {}))
+                                num_stage=nstage, device=str(device), **(dict(args.fusion_options, stats=fstats) if args.fusion_options else {}),
+                                **cloud_keywords(args, fstats))
             if args.fusion_options:
-                print(json.dumps({"scan": scan, "fusion": fusion.fusion_summary(args.fusion_options, fstats,
-                                                                                (args.num_consistency, args.img_dist_thres, args.depth_thres))}))
+                print(json.dumps(dict({"scan": scan, "fusion": fusion.fusion_summary(args.fusion_options, fstats,
+                                                                                     (args.num_consistency, args.img_dist_thres, args.depth_thres))},
+                                      **cloud_summary(fstats))))
+            elif args.cloud_options:
+                print(json.dumps(dict({"scan": scan}, **cloud_summary(fstats))))
             if args.mesh:
                 from . import tsdf_mesh
                 summary = tsdf_mesh.mesh_scan(os.path.join(args.testpath, scan), folder, folder, os.path.join(args.outdir, scan + "_mesh.ply"),
@@ -219,10 +223,13 @@ def run_tanks(model, args, device, rank, world):
         fusion.filter_depth_tanks(os.path.join(args.testpath, args.split, scene), os.path.join(args.outdir, scene), ply, f["geo_pixel_thres"],
                                   f["geo_depth_thres"], f["photo_thres"], img_wh, f["image_size"], f["geo_mask_thres"], args.num_view, scene,
                                   device=str(device), depth_maps=depth_maps, conf_maps=conf_maps,
-                                  **(dict(args.fusion_options, stats=fstats) if args.fusion_options else {}))
+                                  **(dict(args.fusion_options, stats=fstats) if args.fusion_options else {}), **cloud_keywords(args, fstats))
         if args.fusion_options:
-            print(json.dumps({"scene": scene, "fusion": fusion.fusion_summary(args.fusion_options, fstats,
-                                                                               (f["geo_mask_thres"], f["geo_pixel_thres"], f["geo_depth_thres"]))}))
+            print(json.dumps(dict({"scene": scene, "fusion": fusion.fusion_summary(args.fusion_options, fstats,
+                                                                                    (f["geo_mask_thres"], f["geo_pixel_thres"], f["geo_depth_thres"]))},
+                                  **cloud_summary(fstats))))
+        elif args.cloud_options:
+            print(json.dumps(dict({"scene": scene}, **cloud_summary(fstats))))
         if args.mesh:
             from . import tsdf_mesh
             summary = tsdf_mesh.mesh_scan_tanks(os.path.join(args.testpath, args.split, scene), os.path.join(args.outdir, scene),
@@ -247,6 +254,17 @@ def run_tanks(model, args, device, rank, world):
 
 DEDUP_AND_MESH = ("--fusion-dedup does not go with --mesh: the TSDF volume averages EVERY observation of a surface, and suppression keeps "
                   "one view's sample of it and drops the rest; fuse the cloud with --fusion-dedup in one run and mesh in another")
+
+
+def cloud_keywords(args, fstats):
+    """the keywords of filter_depth / filter_depth_tanks for --cloud-radius / --cloud-stat / --cloud-normals: none when none was given"""
+    if not args.cloud_options:
+        return {}
+    return {"clean": args.cloud_options} if args.fusion_options else {"clean": args.cloud_options, "stats": fstats}      # stats: once
+
+
+def cloud_summary(fstats):
+    return {"cloud": fstats["cloud"]} if "cloud" in fstats else {}
 
 
 def mesh_fusion_options(args):
@@ -319,7 +337,7 @@ def main(argv=None):
     ap.add_argument("--num_consistency", type=int, default=3)
     ap.add_argument("--img_dist_thres", type=float, default=0.5)
     ap.add_argument("--depth_thres", type=float, default=0.01)
-    from .fusion import add_fusion_arguments, fusion_options
+    from .fusion import add_fusion_arguments, cloud_options, fusion_options
     add_fusion_arguments(ap)
     ap.add_argument("--outdir", required=True)
     ap.add_argument("--scans", type=int, default=2)
@@ -345,6 +363,9 @@ def main(argv=None):
     if args.dtu_gt and not args.filter:
         raise SystemExit("eval_driver: --dtu-gt scores the clouds of --filter; give both")
     args.fusion_options = fusion_options(args, "eval_driver")
+    args.cloud_options = cloud_options(args, "eval_driver")
+    if args.cloud_options and not tanks and not args.filter:
+        raise SystemExit("eval_driver: --cloud-radius, --cloud-stat and --cloud-normals clean the cloud of the fusion step; give --filter")
     if args.fusion_options and not tanks and not args.filter:
         raise SystemExit("eval_driver: --fusion, --fusion-dedup and --dyn-* set up the fusion step; give --filter")
     if args.fusion_options and args.fusion_options["dedup"] and args.mesh:

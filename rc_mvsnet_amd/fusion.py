@@ -184,6 +184,55 @@ def add_fusion_arguments(ap, dedup=True):
                     help=f"--fusion dynamic: the levels tried (default 2 and the number of source views; at most {MAX_SRC})")
     ap.add_argument("--dyn-dist-base", type=float, default=None, help="--fusion dynamic: reprojection distance of level 1 in pixels (default 0.25)")
     ap.add_argument("--dyn-rel-base", type=float, default=None, help="--fusion dynamic: relative depth difference of level 1 (default 1/1300)")
+    note = " (the fused point cloud only: a mesh is fused from the depth maps, not from the cloud, and ignores this)"
+    ap.add_argument("--cloud-radius", nargs=2, default=None, metavar=("R", "N"), help="keep the points with at least N others within R" + note)
+    ap.add_argument("--cloud-stat", nargs=2, default=None, metavar=("K", "RATIO"),
+                    help="keep the points whose mean distance to their K nearest neighbours is at most mu + RATIO sigma" + note)
+    ap.add_argument("--cloud-normals", type=int, default=None, metavar="K",
+                    help="write nx ny nz from the K nearest neighbours, oriented towards the view that produced the point" + note)
+
+
+def cloud_options(args, who):
+    """The parsed --cloud-radius / --cloud-stat / --cloud-normals -> the ``clean`` keyword of filter_depth / filter_depth_tanks (None when
+    none was given, so that a run without them does what it did before); argument errors end the run with one line."""
+    from . import cloud_clean
+    try:
+        radius = None if args.cloud_radius is None else (float(args.cloud_radius[0]), int(args.cloud_radius[1]))
+        stat = None if args.cloud_stat is None else (int(args.cloud_stat[0]), float(args.cloud_stat[1]))
+    except ValueError:
+        raise SystemExit(f"{who}: --cloud-radius takes a number and an integer, --cloud-stat an integer and a number") from None
+    if radius is not None and not (radius[0] >= 0 and radius[1] >= 0):
+        raise SystemExit(f"{who}: --cloud-radius {radius[0]} {radius[1]}: R >= 0 and N >= 0")
+    if stat is not None and not (1 <= stat[0] <= cloud_clean.MAX_K and stat[1] >= 0):
+        raise SystemExit(f"{who}: --cloud-stat {stat[0]} {stat[1]}: 1 <= K <= {cloud_clean.MAX_K} and RATIO >= 0")
+    if args.cloud_normals is not None and not 1 <= args.cloud_normals <= cloud_clean.MAX_K:
+        raise SystemExit(f"{who}: --cloud-normals {args.cloud_normals}: 1 <= K <= {cloud_clean.MAX_K}")
+    return cloud_clean.clean_options(radius, stat, args.cloud_normals)
+
+
+def camera_centre(extrinsic):
+    """-R^T t of a world-to-camera extrinsic (4,4), in fp64 on the host"""
+    E = np.asarray(extrinsic, dtype=np.float64)
+    return -(E[:3, :3].T @ E[:3, 3])
+
+
+def _write_cloud(plyfilename, pts, cols, centres, clean, stats, dev):
+    """The end of filter_depth / filter_depth_tanks: the per-view points concatenated, cleaned when ``clean`` asks for it (view = the
+    position of the point's reference view in pair.txt, centres = those views' camera centres), and written -> (xyz, rgb) as written."""
+    xyz, rgb = np.concatenate(pts, 0), np.concatenate(cols, 0)
+    normals = None
+    if clean:
+        from . import cloud_clean
+        view = np.repeat(np.arange(len(pts), dtype=np.int32), [len(p) for p in pts])
+        r = cloud_clean.clean_cloud(torch.from_numpy(np.ascontiguousarray(xyz, np.float32)).to(dev), torch.from_numpy(np.ascontiguousarray(rgb, np.uint8)).to(dev),
+                                    torch.from_numpy(view).to(dev), np.stack(centres) if centres else np.zeros((0, 3)), **clean)
+        xyz, rgb = r["xyz"].cpu().numpy(), r["rgb"].cpu().numpy()
+        normals = None if r["normals"] is None else r["normals"].cpu().numpy()
+        if stats is not None:
+            stats["cloud"] = r["stats"]
+    with open(plyfilename, "wb") as f:
+        f.write(ply_bytes(xyz, rgb, normals))
+    return xyz, rgb
 
 
 def fusion_options(args, who):
@@ -290,15 +339,22 @@ def check_geometric_consistency(depth_ref, intrinsics_ref, extrinsics_ref, depth
     return r["geo"][0].cpu().numpy().astype(bool), r["depth_reprojected"][0].cpu().numpy(), xy[..., 0].copy(), xy[..., 1].copy()
 
 
-def ply_bytes(xyz, rgb):
+def ply_bytes(xyz, rgb, normals=None):
     """Binary little-endian PLY with vertex properties x y z (float) red green blue (uchar): the file the reference writes
-    through plyfile (eval_rcmvsnet_dtu.py:433-446)."""
+    through plyfile (eval_rcmvsnet_dtu.py:433-446).  normals (n,3) fp32: the vertex is x y z nx ny nz red green blue, the mesh
+    writer's order (tsdf_mesh.mesh_ply_bytes); dtu_io.read_ply_xyz skips the extra properties."""
     n = len(xyz)
-    head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-            "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % n).encode("ascii")
-    rec = np.empty(n, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    geo = ("x", "y", "z") + (("nx", "ny", "nz") if normals is not None else ())
+    head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n%s"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % (n, "".join("property float %s\n" % k for k in geo))).encode("ascii")
+    rec = np.empty(n, dtype=[(k, "<f4") for k in geo] + [("red", "u1"), ("green", "u1"), ("blue", "u1")])
     for i, k in enumerate(("x", "y", "z")):
         rec[k] = xyz[:, i]
+    if normals is not None:
+        if tuple(np.shape(normals)) != (n, 3):
+            raise _lib.RcmvsError(f"ply_bytes: normals {tuple(np.shape(normals))} for {n} points")
+        for i, k in enumerate(("nx", "ny", "nz")):
+            rec[k] = np.asarray(normals, dtype=np.float32)[:, i]
     for i, k in enumerate(("red", "green", "blue")):
         rec[k] = rgb[:, i]
     return head + rec.tobytes()
@@ -316,14 +372,16 @@ def stage_colour(img, num_stage, shape):
 
 
 def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, prob_threshold, num_consistent, img_dist_thresh, depth_thresh,
-                 num_stage=3, device="cuda:0", save_masks=True, verbose=True, method="reference", dynamic=None, dedup=False, stats=None):
+                 num_stage=3, device="cuda:0", save_masks=True, verbose=True, method="reference", dynamic=None, dedup=False, stats=None, clean=None):
     """eval_rcmvsnet_dtu.py:341-446: fuse one scan into ``plyfilename``; returns (xyz (n,3) fp32, rgb (n,3) uint8).
     method="reference" without dedup is the reference's filter (rcmvs_fuse_view), to the byte.  method="dynamic": the dynamic
     consistency check (fuse_view_dynamic) with the parameters of ``dynamic`` (a dict over DYN_DEFAULTS); prob_threshold stays the
     caller's, num_consistent and the two fixed thresholds are not used.  dedup=True: one point per surface, with either method (for
     "reference" the fixed check runs as one level of the dynamic kernel, see reference_bases); the cloud then depends on the order
     of pair.txt's reference views, which is the order of the launches, and a fourth mask image <view>_claimed.png is written.
-    stats: a dict that receives "views" = [{"ref", "kept", "claimed"}], "kept" and "claimed"."""
+    stats: a dict that receives "views" = [{"ref", "kept", "claimed"}], "kept" and "claimed".
+    clean: a dict of cloud_clean.clean_cloud's options (radius, stat, normals): the concatenated cloud goes through it before the PLY
+    is written (with normals: x y z nx ny nz red green blue), the returned cloud is the one written, and stats gains "cloud"."""
     plain = _check_method(method, dynamic, dedup)
     dev = torch.device(device)
     pairs = scan_io.read_pair_file(os.path.join(pair_folder, "pair.txt"))
@@ -361,9 +419,7 @@ def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, prob_thresho
                     scan_io.save_mask(os.path.join(out_folder, "mask/{:0>8}_{}.png".format(ref, kind)), m[k])
             if verbose:
                 print("processing {}, ref-view{:0>2}, photo/geo/final-mask:{}/{}/{}".format(scan_folder, ref, m[0].mean(), m[1].mean(), m[2].mean()))
-    xyz, rgb = np.concatenate(pts, 0), np.concatenate(cols, 0)
-    with open(plyfilename, "wb") as f:
-        f.write(ply_bytes(xyz, rgb))
+    xyz, rgb = _write_cloud(plyfilename, pts, cols, [camera_centre(cams[ref][1]) for ref, _ in pairs], clean, stats, dev)
     if verbose:
         print("saving the final model to", plyfilename)
     return xyz, rgb
@@ -407,14 +463,15 @@ def _resident(maps, view, dev, what):
 
 def filter_depth_tanks(scan_folder, out_folder, plyfilename, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes,
                        geo_mask_thres, n_views=None, scan="", device="cuda:0", save_masks=True, verbose=True, depth_maps=None,
-                       conf_maps=None, method="reference", dynamic=None, dedup=False, stats=None):
+                       conf_maps=None, method="reference", dynamic=None, dedup=False, stats=None, clean=None):
     """eval_rcmvsnet_tanks.py:269-380, the Tanks-and-Temples form of filter_depth: pair.txt, cams_1/ and images/ live in
     ``scan_folder`` at the ORIGINAL image size ``image_sizes`` = (w, h); the depth maps under ``out_folder`` have the network
     size ``img_wh`` = (w, h), so the intrinsics' first two rows are rescaled and the colour image is resized (cv2.resize's
     rule, on the device).  Same kernels as filter_depth.  depth_maps / conf_maps: optional {view: (H,W) fp32 tensor on ``device``},
     the network's outputs still in HBM; where a view is present its PFM file is not read (PFM holds fp32 losslessly, so the
     cloud is the same to the byte).  method / dynamic / dedup / stats: as filter_depth's; with method="dynamic" photo_thres stays the
-    scene's and geo_mask_thres, geo_pixel_thres and geo_depth_thres are not used.  Returns (xyz (n,3) fp32, rgb (n,3) uint8)."""
+    scene's and geo_mask_thres, geo_pixel_thres and geo_depth_thres are not used.  clean: as filter_depth's.  Returns (xyz (n,3) fp32,
+    rgb (n,3) uint8)."""
     from .mvs_dataset import prepare_image
     plain = _check_method(method, dynamic, dedup)
     dev = torch.device(device)
@@ -473,10 +530,8 @@ def filter_depth_tanks(scan_folder, out_folder, plyfilename, geo_pixel_thres, ge
             if verbose:
                 print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(
                     scan_folder, ref, m[1].mean(), m[0].mean(), m[2].mean()))
-    xyz, rgb = np.concatenate(pts, 0), np.concatenate(cols, 0)
     os.makedirs(os.path.dirname(os.path.abspath(plyfilename)), exist_ok=True)
-    with open(plyfilename, "wb") as f:
-        f.write(ply_bytes(xyz, rgb))
+    xyz, rgb = _write_cloud(plyfilename, pts, cols, [camera_centre(cams[ref][1]) for ref, _ in pairs], clean, stats, dev)
     if verbose:
         print("saving the final model to", plyfilename)
     return xyz, rgb
