@@ -18,7 +18,8 @@ EXT_HEADERS = (os.path.join(CSRC, "pc_register.h"), os.path.join(CSRC, "view_sel
                os.path.join(CSRC, "mesh_decimate.h"), os.path.join(CSRC, "mesh_holes.h"),
                os.path.join(CSRC, "mesh_render.h"), os.path.join(CSRC, "mesh_normals.h"),
                os.path.join(CSRC, "mesh_texture.h"), os.path.join(CSRC, "mesh_simplify.h"),
-               os.path.join(CSRC, "fusion_dyn.h"), os.path.join(CSRC, "cloud_knn.h"))      # entry-point families declared next to their kernels (same grammar as HEADER)
+               os.path.join(CSRC, "fusion_dyn.h"), os.path.join(CSRC, "cloud_knn.h"),
+               os.path.join(CSRC, "poisson.h"))                                          # entry-point families declared next to their kernels (same grammar as HEADER)
 
 _lib = None
 

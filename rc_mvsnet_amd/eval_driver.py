@@ -260,11 +260,12 @@ def cloud_keywords(args, fstats):
     """the keywords of filter_depth / filter_depth_tanks for --cloud-radius / --cloud-stat / --cloud-normals: none when none was given"""
     if not args.cloud_options:
         return {}
-    return {"clean": args.cloud_options} if args.fusion_options else {"clean": args.cloud_options, "stats": fstats}      # stats: once
+    extra = {"poisson": args.poisson_options} if getattr(args, "poisson_options", None) else {}                        # --poisson: the cloud's surface
+    return dict({"clean": args.cloud_options} if args.fusion_options else {"clean": args.cloud_options, "stats": fstats}, **extra)      # stats: once
 
 
 def cloud_summary(fstats):
-    return {"cloud": fstats["cloud"]} if "cloud" in fstats else {}
+    return {k: fstats[k] for k in ("cloud", "poisson") if k in fstats}
 
 
 def mesh_fusion_options(args):
@@ -339,6 +340,12 @@ def main(argv=None):
     ap.add_argument("--depth_thres", type=float, default=0.01)
     from .fusion import add_fusion_arguments, cloud_options, fusion_options
     add_fusion_arguments(ap)
+    ap.add_argument("--poisson", action="store_true",
+                    help="--cloud-normals: Poisson surface of the cleaned cloud (rc_mvsnet_amd.poisson_mesh), written next to it as <scan>_poisson.ply")
+    ap.add_argument("--poisson-resolution", type=int, default=256, metavar="R", help="--poisson: voxels along the longest side of the cloud's scaled box")
+    ap.add_argument("--poisson-trim-relative", type=float, default=None, metavar="F",
+                    help="--poisson: cut the surface where the density is below F times its mean at the points (default: watertight)")
+    ap.add_argument("--poisson-cycles", type=int, default=8, metavar="C", help="--poisson: multigrid cycles")
     ap.add_argument("--outdir", required=True)
     ap.add_argument("--scans", type=int, default=2)
     ap.add_argument("--ref-views", type=int, default=2, help="reference views per scan")
@@ -364,6 +371,10 @@ def main(argv=None):
         raise SystemExit("eval_driver: --dtu-gt scores the clouds of --filter; give both")
     args.fusion_options = fusion_options(args, "eval_driver")
     args.cloud_options = cloud_options(args, "eval_driver")
+    if args.poisson and args.cloud_normals is None:
+        ap.error("--poisson meshes the cloud from its oriented normals; give --cloud-normals K")
+    from . import poisson_mesh
+    args.poisson_options = poisson_mesh.poisson_options(args.poisson, args.poisson_resolution, args.poisson_trim_relative, args.poisson_cycles)
     if args.cloud_options and not tanks and not args.filter:
         raise SystemExit("eval_driver: --cloud-radius, --cloud-stat and --cloud-normals clean the cloud of the fusion step; give --filter")
     if args.fusion_options and not tanks and not args.filter:

@@ -216,9 +216,11 @@ def camera_centre(extrinsic):
     return -(E[:3, :3].T @ E[:3, 3])
 
 
-def _write_cloud(plyfilename, pts, cols, centres, clean, stats, dev):
+def _write_cloud(plyfilename, pts, cols, centres, clean, stats, dev, poisson=None):
     """The end of filter_depth / filter_depth_tanks: the per-view points concatenated, cleaned when ``clean`` asks for it (view = the
-    position of the point's reference view in pair.txt, centres = those views' camera centres), and written -> (xyz, rgb) as written."""
+    position of the point's reference view in pair.txt, centres = those views' camera centres), and written -> (xyz, rgb) as written.
+    poisson: the keywords of poisson_mesh.reconstruct; the cleaned cloud, still on the device, is meshed with them and written next to
+    the cloud as <name>_poisson.ply (needs the normals of ``clean``)."""
     xyz, rgb = np.concatenate(pts, 0), np.concatenate(cols, 0)
     normals = None
     if clean:
@@ -230,6 +232,15 @@ def _write_cloud(plyfilename, pts, cols, centres, clean, stats, dev):
         normals = None if r["normals"] is None else r["normals"].cpu().numpy()
         if stats is not None:
             stats["cloud"] = r["stats"]
+    if poisson is not None:
+        if normals is None:
+            raise _lib.RcmvsError("fusion: poisson needs oriented normals: give clean={'normals': K} (--cloud-normals K)")
+        from . import poisson_mesh, tsdf_mesh
+        verts, faces, col, pstats = poisson_mesh.reconstruct(r["xyz"], r["normals"], r["rgb"], **poisson)
+        with open(os.path.splitext(plyfilename)[0] + "_poisson.ply", "wb") as f:
+            f.write(tsdf_mesh.mesh_ply_bytes(verts, faces, col))
+        if stats is not None:
+            stats["poisson"] = pstats
     with open(plyfilename, "wb") as f:
         f.write(ply_bytes(xyz, rgb, normals))
     return xyz, rgb
@@ -372,7 +383,7 @@ def stage_colour(img, num_stage, shape):
 
 
 def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, prob_threshold, num_consistent, img_dist_thresh, depth_thresh,
-                 num_stage=3, device="cuda:0", save_masks=True, verbose=True, method="reference", dynamic=None, dedup=False, stats=None, clean=None):
+                 num_stage=3, device="cuda:0", save_masks=True, verbose=True, method="reference", dynamic=None, dedup=False, stats=None, clean=None, poisson=None):
     """eval_rcmvsnet_dtu.py:341-446: fuse one scan into ``plyfilename``; returns (xyz (n,3) fp32, rgb (n,3) uint8).
     method="reference" without dedup is the reference's filter (rcmvs_fuse_view), to the byte.  method="dynamic": the dynamic
     consistency check (fuse_view_dynamic) with the parameters of ``dynamic`` (a dict over DYN_DEFAULTS); prob_threshold stays the
@@ -381,7 +392,9 @@ def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, prob_thresho
     of pair.txt's reference views, which is the order of the launches, and a fourth mask image <view>_claimed.png is written.
     stats: a dict that receives "views" = [{"ref", "kept", "claimed"}], "kept" and "claimed".
     clean: a dict of cloud_clean.clean_cloud's options (radius, stat, normals): the concatenated cloud goes through it before the PLY
-    is written (with normals: x y z nx ny nz red green blue), the returned cloud is the one written, and stats gains "cloud"."""
+    is written (with normals: x y z nx ny nz red green blue), the returned cloud is the one written, and stats gains "cloud".
+    poisson: a dict of poisson_mesh.reconstruct's keywords: the cleaned cloud with its normals (clean must ask for them) is meshed from
+    the tensors still on the device, written as <plyfilename without .ply>_poisson.ply, and stats gains "poisson"."""
     plain = _check_method(method, dynamic, dedup)
     dev = torch.device(device)
     pairs = scan_io.read_pair_file(os.path.join(pair_folder, "pair.txt"))
@@ -419,7 +432,7 @@ def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, prob_thresho
                     scan_io.save_mask(os.path.join(out_folder, "mask/{:0>8}_{}.png".format(ref, kind)), m[k])
             if verbose:
                 print("processing {}, ref-view{:0>2}, photo/geo/final-mask:{}/{}/{}".format(scan_folder, ref, m[0].mean(), m[1].mean(), m[2].mean()))
-    xyz, rgb = _write_cloud(plyfilename, pts, cols, [camera_centre(cams[ref][1]) for ref, _ in pairs], clean, stats, dev)
+    xyz, rgb = _write_cloud(plyfilename, pts, cols, [camera_centre(cams[ref][1]) for ref, _ in pairs], clean, stats, dev, poisson)
     if verbose:
         print("saving the final model to", plyfilename)
     return xyz, rgb
@@ -463,7 +476,7 @@ def _resident(maps, view, dev, what):
 
 def filter_depth_tanks(scan_folder, out_folder, plyfilename, geo_pixel_thres, geo_depth_thres, photo_thres, img_wh, image_sizes,
                        geo_mask_thres, n_views=None, scan="", device="cuda:0", save_masks=True, verbose=True, depth_maps=None,
-                       conf_maps=None, method="reference", dynamic=None, dedup=False, stats=None, clean=None):
+                       conf_maps=None, method="reference", dynamic=None, dedup=False, stats=None, clean=None, poisson=None):
     """eval_rcmvsnet_tanks.py:269-380, the Tanks-and-Temples form of filter_depth: pair.txt, cams_1/ and images/ live in
     ``scan_folder`` at the ORIGINAL image size ``image_sizes`` = (w, h); the depth maps under ``out_folder`` have the network
     size ``img_wh`` = (w, h), so the intrinsics' first two rows are rescaled and the colour image is resized (cv2.resize's
@@ -531,7 +544,7 @@ def filter_depth_tanks(scan_folder, out_folder, plyfilename, geo_pixel_thres, ge
                 print("processing {}, ref-view{:0>2}, geo_mask:{:3f} photo_mask:{:3f} final_mask: {:3f}".format(
                     scan_folder, ref, m[1].mean(), m[0].mean(), m[2].mean()))
     os.makedirs(os.path.dirname(os.path.abspath(plyfilename)), exist_ok=True)
-    xyz, rgb = _write_cloud(plyfilename, pts, cols, [camera_centre(cams[ref][1]) for ref, _ in pairs], clean, stats, dev)
+    xyz, rgb = _write_cloud(plyfilename, pts, cols, [camera_centre(cams[ref][1]) for ref, _ in pairs], clean, stats, dev, poisson)
     if verbose:
         print("saving the final model to", plyfilename)
     return xyz, rgb
