@@ -128,12 +128,12 @@ __global__ __launch_bounds__(256) void conv2d_lds_kernel(
     for (int p = 0; p < PPT; ++p)
 #pragma unroll
         for (int c = 0; c < CO / 2; ++c) { acc[p][2 * c] = acc2[p][c].x; acc[p][2 * c + 1] = acc2[p][c].y; }
+    const __amdgpu_buffer_rsrc_t yrs = out_rsrc(y + (long long)n * Ho * Wo * CO, Ho * Wo * CO * 4);      // one image's map (the launcher bounds it)
 #pragma unroll
     for (int p = 0; p < PPT; ++p) {
         const int oy = oy0 + ly + p * TH;
         if (!(oy < Ho && ox < Wo)) continue;
-        const long long op = ((long long)n * Ho + oy) * Wo + ox;
-        float* yp = y + op * CO;
+        const int yo = (oy * Wo + ox) * CO * 4;
         const float* upp = up ? up + (((long long)n * (Ho / 2) + oy / 2) * (Wo / 2) + ox / 2) * CO : nullptr;
         if (scale) {
 #pragma unroll
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void conv2d_lds_kernel(
         }
 #pragma unroll
         for (int co = 0; co < CO; co += 4)
-            *reinterpret_cast<float4*>(yp + co) = make_float4(acc[p][co], acc[p][co + 1], acc[p][co + 2], acc[p][co + 3]);
+            out_store16<RCMVS_OUT_POLICY_CONV2D>(make_float4(acc[p][co], acc[p][co + 1], acc[p][co + 2], acc[p][co + 3]), yrs, yo + co * 4);
     }
 }
 
@@ -226,11 +226,14 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(
     // the tile kernel); after the transpose instruction i of a wave writes float4 i * 64 + lane of the wave's 64 x CO block: 1 KiB contiguous.
     // (TRS = false: plain per-lane stores, for maps so small that the launch is latency-bound and the LDS round trip only adds to it:
     // the 32 -> 32 output conv of stage 1 at 3 x 128 x 160, 11.8 against 13.3 us)
+    // (the descriptor spans the block's own pixels, clipped at the end of the map: the 64-bit part of the address is the block's)
+    const long long p0 = (long long)blockIdx.x * 256;
+    const __amdgpu_buffer_rsrc_t yrs = out_rsrc(y + p0 * CO, (int)(npix - p0 < 256 ? npix - p0 : 256) * CO * 4);
     if constexpr (!TRS) {
         if (live) {
-            float* yp = y + p * CO;
 #pragma unroll
-            for (int co = 0; co < CO; co += 4) *reinterpret_cast<float4*>(yp + co) = make_float4(acc[co], acc[co + 1], acc[co + 2], acc[co + 3]);
+            for (int co = 0; co < CO; co += 4)
+                out_store16<RCMVS_OUT_POLICY_CONV2D>(make_float4(acc[co], acc[co + 1], acc[co + 2], acc[co + 3]), yrs, ((int)threadIdx.x * CO + co) * 4);
         }
     } else {
         constexpr int STR = CO + 4;                                     // floats per pixel row in LDS (16-byte aligned, bank-staggered)
@@ -239,12 +242,12 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(
 #pragma unroll
         for (int co = 0; co < CO; co += 4) *reinterpret_cast<f4v*>(tw + lane * STR + co) = (f4v){acc[co], acc[co + 1], acc[co + 2], acc[co + 3]};
         __builtin_amdgcn_wave_barrier();
-        const long long wbase = (long long)blockIdx.x * 256 + (threadIdx.x & ~63);      // first pixel of this wave
+        const int wbase = threadIdx.x & ~63;                            // first pixel of this wave inside the block
 #pragma unroll
         for (int i = 0; i < CO / 4; ++i) {
             const int e = i * 64 + lane, px = e / (CO / 4), q = e % (CO / 4);
             const f4v v = *reinterpret_cast<const f4v*>(tw + px * STR + q * 4);
-            if (wbase + px < npix) *reinterpret_cast<f4v*>(y + (wbase + px) * CO + q * 4) = v;
+            out_store16<RCMVS_OUT_POLICY_CONV2D>(v, yrs, p0 + wbase + px < npix ? ((wbase + px) * CO + q * 4) * 4 : OUT_OOB);
         }
     }
     if (ysq) {
@@ -295,6 +298,7 @@ static int conv2d_launch_t(const float* x, const float* wp, const float* scale, 
     const int tiles_w = (Wo + TW - 1) / TW, tiles_h = (Ho + TH * PPT - 1) / (TH * PPT);
     constexpr int HH = (TH * PPT - 1) * S + K, HW = (TW - 1) * S + K;
     const size_t lds = (size_t)HH * HW * C2_STRIDE * sizeof(float);
+    if (!out_span_ok((long long)Ho * Wo * CO * 4)) return fail(-1, "conv2d: one image's output map (%d x %d x %d) does not fit a 32-bit byte offset", Ho, Wo, CO);
     hipLaunchKernelGGL((conv2d_lds_kernel<CI, CO, K, S, TH, TW, PPT, UKY, UKX, RGB3>), dim3(tiles_w * tiles_h, N), dim3(256), lds, st, x, wp, scale,
                        shift, up, y, H, W, Ho, Wo, tiles_w, relu);
     return launch_status("conv2d");
@@ -370,6 +374,9 @@ __global__ __launch_bounds__(256) void conv1x1_mfma_kernel(
         fetch(tile + stride);
         const long long p = tile * 16 + n;
         const bool live = p < npix;
+        // (the descriptor spans the n-tile's own 16 pixels, clipped at the end of the map; the tile index is the wave's)
+        const long long t0 = uniform_ll(tile) * 16;
+        const __amdgpu_buffer_rsrc_t yrs = out_rsrc(y + t0 * CO, (int)(npix - t0 < 16 ? npix - t0 : 16) * CO * 4);
         long long upo = 0;
         if (up && live) {                                                // F.interpolate(intra) + inner(conv): pixel (b, oy, ox) <- up[b, oy / 2, ox / 2]
             const long long b = p / hw;
@@ -392,7 +399,7 @@ __global__ __launch_bounds__(256) void conv1x1_mfma_kernel(
             if (live) {
                 if (up) v = *reinterpret_cast<const x3_f32x4*>(up + upo + co) + v;
                 if (relu) v = __builtin_elementwise_max(v, (x3_f32x4){0.f, 0.f, 0.f, 0.f});
-                *reinterpret_cast<x3_f32x4*>(y + p * CO + co) = v;
+                out_store16<RCMVS_OUT_POLICY_CONV2D>(v, yrs, (n * CO + co) * 4);
                 vmax = x3_absmax4(vmax, v);
             }
         }

@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_pair_kernel(
         for (int p = 0; p < 3; ++p) A[j][p] = wimg[((P2_KS + j) * 3 + p) * 64 + lane];
     __syncthreads();
     // ---- second layer on the 8 x 30 output tile: rows wave, wave + 4 (the second n-tile of a row holds 14 pixels)
-    float* yb = y + (long long)view * H * W * P2_C;
+    const __amdgpu_buffer_rsrc_t yrs = out_rsrc(y + (long long)view * H * W * P2_C, H * W * P2_C * 4);       // one view's map (the launcher bounds it)
 #pragma unroll 1
     for (int r = wave; r < P2_TH; r += 4) {
         const int base[2] = {(r * P2_MW + n) * P2_PB, (r * P2_MW + 16 + n) * P2_PB};
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_pair_kernel(
             x3_f32x4 v = acc[t] * scb + shb;
             v = __builtin_elementwise_max(v, (x3_f32x4){0.f, 0.f, 0.f, 0.f});
             const int oh = h0 + r, ow = w0 + c0 + n;
-            if (c0 + n < P2_TW && oh < H && ow < W) *reinterpret_cast<x3_f32x4*>(yb + ((long long)oh * W + ow) * P2_C + 4 * g4) = v;
+            out_store16<RCMVS_OUT_POLICY_PAIR>(v, yrs, (c0 + n < P2_TW && oh < H && ow < W) ? ((oh * W + ow) * P2_C + 4 * g4) * 4 : OUT_OOB);
         }
     }
 }

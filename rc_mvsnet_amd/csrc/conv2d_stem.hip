@@ -161,7 +161,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_stem_kernel(
     __syncthreads();
     // ---- 3. second layer on the 14 x 30 output tile: a wave takes rows wave, wave + 4, wave + 8, wave + 12, two at a time (independent accumulator chains)
     const int col = 2 * n + s;
-    float* yb = y + ((long long)view * H * W + (long long)h0 * W + w0 + col) * 8 + c4;
+    const __amdgpu_buffer_rsrc_t yrs = out_rsrc(y + (long long)view * H * W * 8, H * W * 32);        // one view's map (the launcher bounds it)
+    const int yo = (((h0 * W + w0 + col) * 8) + c4) * 4;
     const bool colin = col < ST_TW && w0 + col < W;
     const int boff = (2 * n + kk) * 16;                         // lane (n, kk): the 8 channels of column 2 n + kk
 #pragma unroll 1
@@ -195,7 +196,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_stem_kernel(
         for (int u = 0; u < 2; ++u) {
             x3_f32x4 v = (a0[u] + (a1[u] + a2[u])) * scb + shb;
             v = __builtin_elementwise_max(v, (x3_f32x4){0.f, 0.f, 0.f, 0.f});
-            if (colin && rows[u] < ST_TH && h0 + rows[u] < H) *reinterpret_cast<x3_f32x4*>(yb + (long long)rows[u] * W * 8) = v;
+            out_store16<RCMVS_OUT_POLICY_STEM>(v, yrs, (colin && rows[u] < ST_TH && h0 + rows[u] < H) ? yo + rows[u] * W * 32 : OUT_OOB);
         }
     }
 }
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_stem_kernel(
 // writes it with the input channels padded to four ([9][4][8]); wimg: conv2d_stem_pack's image of the second layer
 int conv2d_stem_launch(const float* x, const float* wa, const float* sa, const float* ha, const float* wimg, const float* sb, const float* hb, float* y,
                        int N, int H, int W, hipStream_t st) {
-    if ((long long)H * W * 8 * 4 >= 0x7ffffff0LL || N > 65535) return fail(-1, "conv2d_stem: map too large");
+    if ((long long)H * W * 8 * 4 >= 0x7ffffff0LL || N > 65535) return fail(-1, "conv2d_stem: map too large for 32-bit offsets");
     const int tw_ = (W + ST_TW - 1) / ST_TW, th_ = (H + ST_TH - 1) / ST_TH;
     hipLaunchKernelGGL(conv2d_stem_kernel, dim3(tw_ * th_, N), dim3(256), ST_LDS, st, x, wa, sa, ha, reinterpret_cast<const x3_u32x4*>(wimg), sb, hb, y, H, W, tw_);
     return launch_status("conv2d_stem");

@@ -100,7 +100,7 @@ __global__ __launch_bounds__(CO * 16, CO == 16 ? 2 : 1) void conv2d_tile_kernel(
     if (tid < T2_IH * 16) park(pf[NR], er, ec);
     __syncthreads();
     // ---- rows 2 rg, 2 rg + 1 (rg = this wave's row pair): the two n-tiles of a row together (independent accumulator chains); lane (n, kk) supplies channels 8 kk .. of pixel (row + dy, column + dx)
-    float* yb = y + (long long)view * H * W * CO;
+    const __amdgpu_buffer_rsrc_t yrs = out_rsrc(y + (long long)view * H * W * CO, H * W * CO * 4);   // one view's map (CO <= T2_CI: the launcher's bound covers it)
     float vmax = 0.0f;
 #pragma unroll 1
     for (int rr = 0; rr < 2; ++rr) {
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(CO * 16, CO == 16 ? 2 : 1) void conv2d_tile_kernel(
             if (relu) v = __builtin_elementwise_max(v, (x3_f32x4){0.f, 0.f, 0.f, 0.f});
             const int oh = h0 + row, ow = w0 + 16 * t + n;
             if (oh < H && ow < W) {
-                *reinterpret_cast<x3_f32x4*>(yb + ((long long)oh * W + ow) * CO + co0) = v;
+                out_store16<RCMVS_OUT_POLICY_TILE>(v, yrs, ((oh * W + ow) * CO + co0) * 4);
                 vmax = x3_absmax4(vmax, v);
             }
         }

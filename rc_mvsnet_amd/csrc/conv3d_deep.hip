@@ -256,9 +256,12 @@ __global__ __launch_bounds__(512) void conv3d_deep_kernel(
     // B fragments: lane (n, kq) reads 16 bytes of cell (row 2t + (n >> 3), column n & 7) at the tap's offset, one step ahead (two
     // register sets, pinned with sched_barrier: left alone the scheduler sinks every ds_read to just before its MFMAs)
     static_assert(PF % 2 == 0, "the B double buffer alternates with the step parity");
+    // output: the descriptor of this block's batch element (the 64-bit part of the address is in its base)
+    const long long yb0 = (long long)b * dm.Do * dm.Ho * dm.Wo * COUT;
+    const __amdgpu_buffer_rsrc_t yrs = out_rsrc(y + yb0, dm.Do * dm.Ho * dm.Wo * COUT * 4);
     int bb[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) bb[t] = (((2 * t + (n >> 3)) * C::CS) * C::HW + (n & 7) * C::CS) * VS + (C::TPS == 2 ? (kq & 1) : kq) * 16;
+    for (int t = 0; t < NT; ++t) bb[t] =(((2 * t + (n >> 3)) * C::CS) * C::HW + (n & 7) * C::CS) * VS + (C::TPS == 2 ? (kq & 1) : kq) * 16;
     float vmax = 0.0f;
 #pragma unroll
     for (int sg = 0; sg < (KIND == DP_T2 ? 3 : 1); ++sg) {           // (unrolled: the ring of a segment is a compile-time choice)
@@ -356,11 +359,11 @@ __global__ __launch_bounds__(512) void conv3d_deep_kernel(
                 const int ch = h0 + 2 * t + (n >> 3), cw = w0 + (n & 7);
                 if (ch >= dm.Hg || cw >= dm.Wg) continue;
                 const int od = KIND == DP_T2 ? 2 * dg + pd : dg, oh = KIND == DP_T2 ? 2 * ch + ph : ch, ow = KIND == DP_T2 ? 2 * cw + pw : cw;
-                const long long ov = ((((long long)b * dm.Do + od) * dm.Ho + oh) * dm.Wo + ow) * COUT + co;
+                const int oe = ((od * dm.Ho + oh) * dm.Wo + ow) * COUT + co;             // inside the batch element's volume (the launcher bounds it)
                 x3_f32x4 v = tot[t] * sc + sh;
                 if (dm.relu) v = __builtin_elementwise_max(v, (x3_f32x4){0.f, 0.f, 0.f, 0.f});
-                if (res) v += *reinterpret_cast<const x3_f32x4*>(res + ov);
-                *reinterpret_cast<x3_f32x4*>(y + ov) = v;
+                if (res) v += *reinterpret_cast<const x3_f32x4*>(res + yb0 + oe);
+                out_store16<RCMVS_OUT_POLICY_DEEP>(v, yrs, oe * 4);
                 vmax = x3_absmax4(vmax, v);
             }
         }
@@ -469,6 +472,7 @@ int conv3d_deep_launch(const float* x, const float* wimg, const float* scale, co
         dm.Dg = dm.Do; dm.Hg = dm.Ho; dm.Wg = dm.Wo;
     }
     if ((long long)B * D * H * W * Ci * 4 >= 0x7ffffff0LL) return fail(-1, "conv3d_deep: input tensor too large for 32-bit offsets");
+    if (!out_span_ok((long long)dm.Do * dm.Ho * dm.Wo * Co * 4)) return fail(-1, "conv3d_deep: one batch element's output does not fit a 32-bit byte offset");
     dm.tiles_h = dm.tiles_w = 0;                   // (per instantiation: deep_launch_t)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return fail(-1, "conv3d_deep: cannot query the device");

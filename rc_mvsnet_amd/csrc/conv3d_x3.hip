@@ -510,7 +510,7 @@ __global__ __launch_bounds__(512) void conv3d_x3_kernel(
                 v = v * esc[i] + esh[i];
                 if (relu) v = __builtin_elementwise_max(v, (x3_f32x4){0.f, 0.f, 0.f, 0.f});
                 v += erv[i];
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(x3_u32x4, v), yrs, X3_DBG(3) ? OOB : eob[i], 0, 0);
+                out_store16<RCMVS_OUT_POLICY_X3>(v, yrs, X3_DBG(3) ? OOB : eob[i]);
                 if (ymax && eob[i] != OOB) vmax = x3_absmax4(vmax, v);
             }
         }
@@ -673,7 +673,7 @@ __global__ __launch_bounds__(512) void conv3d_x3_kernel(
                             if (relu) v = __builtin_elementwise_max(v, (x3_f32x4){0.f, 0.f, 0.f, 0.f});
                             v += rv[t][mt];
                             const int ob = cob[TP * tp + t][mt];
-                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(x3_u32x4, v), yrs, X3_DBG(3) ? OOB : ob, 0, 0);
+                            out_store16<RCMVS_OUT_POLICY_X3>(v, yrs, X3_DBG(3) ? OOB : ob);
                             if (ymax && ob != OOB) vmax = x3_absmax4(vmax, v);
                         }
                     }

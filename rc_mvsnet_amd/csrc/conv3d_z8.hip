@@ -278,7 +278,7 @@ __global__ __launch_bounds__(512) void conv3d_z8_kernel(
                     if (dm.relu) v = __builtin_elementwise_max(v, (x3_f32x4){0.f, 0.f, 0.f, 0.f});
                     // (a buffer store with an out-of-range offset for lanes outside the volume: a fixed number of vector-memory operations per
                     // tick, so the compiler's s_waitcnt bookkeeping can wait for the two-tick-old plane with a partial count)
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(x3_u32x4, v), yrs, ob[i], 0, 0);
+                    out_store16<RCMVS_OUT_POLICY_Z8>(v, yrs, ob[i]);
                     const bool in = ob[i] != OOB;
                     vmax = in ? x3_absmax4(vmax, v) : vmax;
                     ob[i] = in ? ob[i] + ostep : OOB;
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(512) void conv3d_z8_kernel(
                 for (int i = 0; i < C::NTW; ++i) {
                     x3_f32x4 v = acc[i][1] * sc + sh;
                     if (dm.relu) v = __builtin_elementwise_max(v, (x3_f32x4){0.f, 0.f, 0.f, 0.f});
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(x3_u32x4, v), yrs, ob[i], 0, 0);
+                    out_store16<RCMVS_OUT_POLICY_Z8>(v, yrs, ob[i]);
                     vmax = ob[i] != OOB ? x3_absmax4(vmax, v) : vmax;
                 }
             }

@@ -232,7 +232,7 @@ __global__ __launch_bounds__(512) void conv3d_zs2_kernel(
             x3_f32x4 v = (cur[i][0] + cur[i][1]) * sc + sh;
             if (dm.relu) v = __builtin_elementwise_max(v, (x3_f32x4){0.f, 0.f, 0.f, 0.f});
             const bool in = !lead && ob[i] != OOB;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(x3_u32x4, v), yrs, in ? ob[i] : OOB, 0, 0);
+            out_store16<RCMVS_OUT_POLICY_ZS2>(v, yrs, in ? ob[i] : OOB);
             vmax = in ? x3_absmax4(vmax, v) : vmax;
             ob[i] = in ? ob[i] + ostep : ob[i];
             cur[i][0] = nxt[i][0]; cur[i][1] = nxt[i][1];

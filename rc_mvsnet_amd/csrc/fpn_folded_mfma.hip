@@ -76,6 +76,7 @@ __global__ __launch_bounds__(256, 2) void fpn_folded_mfma_kernel(
     const int ntiles = N * tiles_h * tiles_w;
     __amdgpu_buffer_rsrc_t lrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(lat), (short)0, (int)((long long)N * H * W * 32), 0x00020000);
     __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(up), (short)0, (int)((long long)N * Hh * Wh * 128), 0x00020000);
+    const __amdgpu_buffer_rsrc_t yrs = out_rsrc(y, (int)((long long)N * H * W * 32));                  // (as large as `lat`: the entry point bounds it)
     // weight fragments of this row parity: 3 (lateral rows) + 6 (`prev`: 2 rows x 3 columns) k-steps x 3 pieces
     x3_u32x4 A[9][3];
 #pragma unroll
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void fpn_folded_mfma_kernel(
                 const int cy = oy == 0 ? 0 : (oy == H - 1 ? 2 : 1), cx = ox == 0 ? 0 : (ox == W - 1 ? 2 : 1);
                 const x3_f32x4 bs = *reinterpret_cast<const x3_f32x4*>(bias + (cy * 3 + cx) * 8 + (kq & 1) * 4);
                 const x3_f32x4 v = (acc[0] + (acc[1] + acc[2])) + bs;
-                *reinterpret_cast<x3_f32x4*>(y + (((long long)b * H + oy) * W + ox) * 8 + (kq & 1) * 4) = v;
+                out_store16<RCMVS_OUT_POLICY_FPN>(v, yrs, ((((b * H + oy) * W + ox) * 8) + (kq & 1) * 4) * 4);
                 vmax = x3_absmax4(vmax, v);
             }
         }

@@ -41,7 +41,11 @@ __global__ __launch_bounds__(256) void layout_kernel(const float* __restrict__ s
         v.y = pl[(4LL * q + 1) * S + s];
         v.z = pl[(4LL * q + 2) * S + s];
         v.w = pl[(4LL * q + 3) * S + s];
-        *reinterpret_cast<float4*>(dst + ((long long)n * S + s) * C + 4 * q) = v;
+        // (the descriptor spans the positions this block's threads can hold, clipped at the end of the image: everything 64-bit is in its base)
+        const long long s0 = (long long)blockIdx.x * blockDim.x / (64LL * Q) * 64;
+        const long long cap = 64LL * (blockDim.x / (64 * Q) + 2), ns = S - s0 < cap ? S - s0 : cap;
+        const __amdgpu_buffer_rsrc_t drs = out_rsrc(dst + ((long long)n * S + s0) * C, (int)ns * C * 4);
+        out_store16<RCMVS_OUT_POLICY_LAYOUT>(v, drs, ((int)(s - s0) * C + 4 * q) * 4);
     } else {
         float4 v = *reinterpret_cast<const float4*>(src + ((long long)n * S + s) * C + 4 * q);
         float* o = dst + (long long)n * C * S;
@@ -70,6 +74,7 @@ template <bool TO_LAST>
 static int layout_launch(const float* src, float* dst, int N, int C, long long S, void* stream) {
     RCMVS_REQUIRE(src && dst && N > 0 && C > 0 && S > 0, "layout: bad arguments N=%d C=%d S=%lld", N, C, S);
     if (C % 4 == 0) {
+        if (TO_LAST && !out_span_ok(64LL * (256 / (16LL * C) + 2) * C * 4)) return fail(-1, "layout: C=%d is too many channels for a block's 32-bit offsets", C);
         long long threads = cdiv(S, 64) * 64 * (C / 4);
         dim3 grid((unsigned)cdiv(threads, 256), N);
         hipLaunchKernelGGL(layout_kernel<TO_LAST>, grid, dim3(256), 0, as_stream(stream), src, dst, C, S);

@@ -97,7 +97,9 @@ __global__ __launch_bounds__(256) void warp_variance_pp_kernel(
     const v4f ref2 = ref * ref;
     const float rV = rcp_nr((float)V);
     const long long pstride = (long long)hw * C;
-    float* ob = var + (((long long)b * D + k0) * hw + (long long)min(y, h - 1) * w + min(x, w - 1)) * C + (q4b >> 2);
+    // output: one descriptor per plane (its base carries batch element and plane, the 64-bit part), this lane's byte offset inside the plane
+    float* const vb = var + ((long long)b * D + k0) * pstride;
+    const int oo = (min(y, h - 1) * w + min(x, w - 1)) * TEXB + q4b;
     const int pitch = w * TEXB;
 
     records(0, 0);
@@ -136,7 +138,7 @@ __global__ __launch_bounds__(256) void warp_variance_pp_kernel(
         if (inside && k0 + k < D) {
             const v4f m = a * rV;
             const v4f o = __builtin_elementwise_fma(a2, (v4f){rV, rV, rV, rV}, -(m * m));
-            __builtin_nontemporal_store(o, reinterpret_cast<v4f*>(ob + k * pstride));
+            out_store16<RCMVS_OUT_POLICY_K1>(o, out_rsrc(vb + k * pstride, hw * TEXB), oo);
         }
         if (k + 1 < DKB) __syncthreads();
     }

@@ -99,7 +99,9 @@ __global__ __launch_bounds__(256) void warp_variance_win_kernel(
     const v4f ref2 = ref * ref;
     const float rV = rcp_nr((float)V);
     const long long pstride = (long long)hw * C;
-    float* ob = var + ((long long)b * D * hw + (long long)min(y, h - 1) * w + min(x, w - 1)) * C + (q4b >> 2);
+    // output: one descriptor per plane (its base carries batch element and plane, the 64-bit part), this lane's byte offset inside the plane
+    float* const vb = var + (long long)b * D * pstride;
+    const int oo = (min(y, h - 1) * w + min(x, w - 1)) * TEXB + q4b;
     const int pitch = w * TEXB;
     const int xcen = min(tx0 + TW / 2, w - 1), ycen = min(ty0 + TH / 2, h - 1);
     const float fxc = (float)xcen, fyc = (float)ycen, fxa = (float)xa, fya = (float)ya;
@@ -223,7 +225,7 @@ __global__ __launch_bounds__(256) void warp_variance_win_kernel(
                 if (k0 + k < D) {
                     const v4f m = a * rV;
                     const v4f o = __builtin_elementwise_fma(a2, (v4f){rV, rV, rV, rV}, -(m * m));
-                    __builtin_nontemporal_store(o, reinterpret_cast<v4f*>(ob + (k0 + k) * pstride));
+                    out_store16<RCMVS_OUT_POLICY_K1>(o, out_rsrc(vb + (k0 + k) * pstride, hw * TEXB), oo);
                 }
             };
             Taps f0, f1;

@@ -213,7 +213,7 @@ __device__ __forceinline__ void k1_issue(K1Fetch<NV>& f, const v4i* lds_o, const
 }
 
 template <bool FAST>
-__device__ __forceinline__ void k1_store_variance(v4f a, v4f a2, float fV, float rV, float* dst) {
+__device__ __forceinline__ void k1_store_variance(v4f a, v4f a2, float fV, float rV, float* plane, int plane_bytes, int off) {      // plane: wave-uniform
 #pragma clang fp contract(off)
     v4f m, o;
     m.x = div_c<1>(a.x, fV, rV); m.y = div_c<1>(a.y, fV, rV); m.z = div_c<1>(a.z, fV, rV); m.w = div_c<1>(a.w, fV, rV);
@@ -221,7 +221,7 @@ __device__ __forceinline__ void k1_store_variance(v4f a, v4f a2, float fV, float
     o.y = div_c<1>(a2.y, fV, rV) - m.y * m.y;
     o.z = div_c<1>(a2.z, fV, rV) - m.z * m.z;
     o.w = div_c<1>(a2.w, fV, rV) - m.w * m.w;
-    __builtin_nontemporal_store(o, reinterpret_cast<v4f*>(dst));
+    out_store16<RCMVS_OUT_POLICY_K1>(o, out_rsrc(plane, plane_bytes), off);
 }
 
 // Common prologue of the two kernels below: geometry constants, the block's tile and the two thread identities.
@@ -292,7 +292,8 @@ __global__ __launch_bounds__(256) void warp_variance_tp_kernel(
     v4f ref = (v4f){0.f, 0.f, 0.f, 0.f};
     if (inside) ref = *reinterpret_cast<const v4f*>(fb + ((long long)y * w + x) * C + (q4b >> 2));
     const float fV = (float)V, rV = rcp_nr(fV);
-    float* ob = var + (((long long)b * D) * hw + (long long)y * w + x) * C + (q4b >> 2);
+    float* const vb = var + (long long)b * D * hw * C;             // output: a descriptor per plane (batch element and plane in its base), this lane's offset inside it
+    const int oo = (y * w + x) * C * 4 + q4b;
     // ---------------- phase A
     {
         const int pa = threadIdx.x % PIX;
@@ -325,7 +326,7 @@ __global__ __launch_bounds__(256) void warp_variance_tp_kernel(
             a = a + val;
             if (FAST) a2 = __builtin_elementwise_fma(val, val, a2); else a2 = a2 + val * val;
         }
-        if (gi == NGRP - 1 && k0 + k < D) k1_store_variance<FAST>(a, a2, fV, rV, ob + (long long)(k0 + k) * hw * C);
+        if (gi == NGRP - 1 && k0 + k < D) k1_store_variance<FAST>(a, a2, fV, rV, vb + (long long)(k0 + k) * hw * C, hw * C * 4, oo);
     }
 }
 
@@ -358,7 +359,8 @@ __global__ __launch_bounds__(256) void warp_variance_mv_kernel(
     v4f ref = (v4f){0.f, 0.f, 0.f, 0.f};
     if (inside) ref = *reinterpret_cast<const v4f*>(fb + ((long long)y * w + x) * C + (q4b >> 2));
     const float fV = (float)V, rV = rcp_nr(fV);
-    float* ob = var + (((long long)b * D) * hw + (long long)y * w + x) * C + (q4b >> 2);
+    float* const vb = var + (long long)b * D * hw * C;             // output: a descriptor per plane (batch element and plane in its base), this lane's offset inside it
+    const int oo = (y * w + x) * C * 4 + q4b;
     const int pa = threadIdx.x % PIX;
     const int xa = min(tx0 + pa % TW, w - 1), ya = min(ty0 + pa / TW, h - 1);
     const float2 pla = reinterpret_cast<const float2*>(planes)[(long long)b * hw + ya * w + xa];
@@ -383,7 +385,7 @@ __global__ __launch_bounds__(256) void warp_variance_mv_kernel(
                 if (FAST) a2 = __builtin_elementwise_fma(val, val, a2); else a2 = a2 + val * val;
             }
             if (v0 + nv < V) { s[k] = a; sq[k] = a2; continue; }
-            if (k0 + k < D) k1_store_variance<FAST>(a, a2, fV, rV, ob + (long long)(k0 + k) * hw * C);
+            if (k0 + k < D) k1_store_variance<FAST>(a, a2, fV, rV, vb + (long long)(k0 + k) * hw * C, hw * C * 4, oo);
         }
     }
 }
